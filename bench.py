@@ -20,6 +20,12 @@ exchange step).  Total work is fixed, so scaling is "strong".
 value = actual camera samples in the frame (sum of the per-pixel sampleCountBuffer, i.e.
 adaptive-aware) x steps / max-over-ranks wall time.
 
+A plain run sets up, warms up, times the steps and prints the line.  --dump-outputs DIR also
+writes the frame of the last timed step (dump_outputs).  --full adds everything else, after the
+timed steps: the work-counting passes with the proof audit, the rooflines, the bit-for-bit check
+of the timed frame against the reference goldens (a mismatch or an audit violation is a non-zero
+exit) and the CPU baseline.
+
 Prints ONE JSON line (rank 0).
 """
 import argparse
@@ -256,6 +262,28 @@ def cpu_baseline(wl, threads, row_stride, scene_path, camera_path, env=None):
     return out
 
 
+DUMP_MAX_PIXELS = 1 << 21  # --dump-outputs: 16 B per pixel (f32 rgb + f32 count), 32 MiB in all
+
+
+def dump_outputs(path, rgb, cnt):
+    """Write what a caller of the timed path receives from its last step -- the frame's radiance
+    (rgb [H][W][3] f32) and per-pixel sample counts (cnt [H][W] i32, exact in f32) -- as
+    path/rgb.npy and path/count.npy, both float32.  A frame of more than DUMP_MAX_PIXELS pixels is
+    written as that many of its pixels, drawn without replacement by a fixed seed and sorted
+    ([n][3] and [n]); the inputs are files and a keyed RNG, so two runs with the same arguments
+    write the same arrays."""
+    os.makedirs(path, exist_ok=True)
+    h, w = cnt.shape
+    rgb, cnt = rgb.reshape(h * w, 3), cnt.reshape(h * w)
+    if h * w > DUMP_MAX_PIXELS:
+        pick = np.sort(np.random.default_rng(0).choice(h * w, DUMP_MAX_PIXELS, replace=False))
+        rgb, cnt = rgb[pick], cnt[pick]
+    else:
+        rgb, cnt = rgb.reshape(h, w, 3), cnt.reshape(h, w)
+    np.save(os.path.join(path, "rgb.npy"), np.ascontiguousarray(rgb, dtype=np.float32))
+    np.save(os.path.join(path, "count.npy"), np.ascontiguousarray(cnt, dtype=np.float32))
+
+
 def wl_name(wl):
     return next(k for k, v in WORKLOADS.items() if v is wl)
 
@@ -307,7 +335,7 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="cfg3", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--variant", type=int, default=0, help="rrt_render_params.variant (A/B: waves per SIMD)")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--cpu-row-stride", type=int, default=0, help="0 = the workload's default")
@@ -317,6 +345,13 @@ def main():
     ap.add_argument("--pmc", default=None,
                     help="PMC FP64 VALU counters per launch (tools/pmc_valu.py) for the fp64_valu roofline; "
                          "default profiles/r0N_<workload>_pmc.json, newest round first")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the two "
+                         "work-counting passes and the proof audit, the rooflines, the bit-for-bit check of the "
+                         "timed frame against the reference goldens and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the frame of the last timed step as DIR/rgb.npy and DIR/count.npy (float32; a "
+                         "fixed seeded sample of the pixels when the frame is larger than the size cap)")
     a = ap.parse_args()
 
     mode = check_world(a.gpus)
@@ -416,6 +451,11 @@ def main():
 
     kernel_name = r.stats().kernel.decode()
 
+    # the frame's actual camera samples: rank 0 holds the gathered sampleCountBuffer
+    samples = float(frame_cnt.to(torch.int64).sum().item()) if rank == 0 else None
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, frame_rgb.view(H, W, 3).cpu().numpy(), frame_cnt.view(H, W).cpu().numpy())
+
     # work of this rank's launch, counted by the counting kernel outside the timed region: the
     # work the renderer executes (roofline) and the reference algorithm's work
     n_loc = len(tiles)
@@ -435,36 +475,59 @@ def main():
             dist.all_reduce(t)
         return [float(v) for v in t.cpu().numpy()], c4
 
-    (samples, bbox, micro, prim, queries, pixels), _ = count_pass(0)
-    # the executed-work pass runs the proofs: audit every 1024th proven ray (and pixel) exactly
-    r.set_proof_audit(AUDIT_EVERY_LOG2)
-    (_, x_bbox, x_micro, x_prim, x_plane, _), xc4 = count_pass(rrt.RRT_RENDER_COUNT_EXECUTED)
-    r.set_proof_audit(-1)
-    audit = r.proof_audit()
-    if world > 1:
-        at = torch.tensor([[v["checked"], v["violations"]] for v in audit.values()], dtype=torch.float64, device=dev)
-        dist.all_reduce(at)
-        audit = {k: {"checked": int(at[i, 0]), "violations": int(at[i, 1])} for i, k in enumerate(audit)}
-    audit_violations = sum(v["violations"] for v in audit.values())
-    loc_bytes = BYTES_AABB * xc4[0] + BYTES_PRIM * xc4[2] + BYTES_PLANE * xc4[3] + BYTES_PIXEL * pix_local
-    ref_bytes = BYTES_AABB * bbox + BYTES_PRIM * prim + BYTES_PIXEL * pixels
-    main_kernel = kernel_name.split(" + ")[-1]
-    traffic = find_profile(a.traffic, [f"{r}_traffic_{a.workload}.json" for r in PROFILE_ROUNDS], a.workload, kernel_name)
-    pmc = find_profile(a.pmc, [f"{r}_{a.workload}_pmc.json" for r in PROFILE_ROUNDS], a.workload, main_kernel)
-
-    verified = None
-    if rank == 0:
+    def full_report():
+        """What --full adds to the line (every rank takes part; rank 0's dict is printed) ->
+        (fields, verified, proof-audit violations)."""
+        (counted, bbox, micro, prim, queries, pixels), _ = count_pass(0)
+        # the executed-work pass runs the proofs: audit every 1024th proven ray (and pixel) exactly
+        r.set_proof_audit(AUDIT_EVERY_LOG2)
+        (_, x_bbox, x_micro, x_prim, x_plane, _), xc4 = count_pass(rrt.RRT_RENDER_COUNT_EXECUTED)
+        r.set_proof_audit(-1)
+        audit = r.proof_audit()
+        if world > 1:
+            at = torch.tensor([[v["checked"], v["violations"]] for v in audit.values()], dtype=torch.float64,
+                              device=dev)
+            dist.all_reduce(at)
+            audit = {k: {"checked": int(at[i, 0]), "violations": int(at[i, 1])} for i, k in enumerate(audit)}
+        violations = sum(v["violations"] for v in audit.values())
+        loc_bytes = BYTES_AABB * xc4[0] + BYTES_PRIM * xc4[2] + BYTES_PLANE * xc4[3] + BYTES_PIXEL * pix_local
+        ref_bytes = BYTES_AABB * bbox + BYTES_PRIM * prim + BYTES_PIXEL * pixels
+        main_kernel = kernel_name.split(" + ")[-1]
+        traffic = find_profile(a.traffic, [f"{r}_traffic_{a.workload}.json" for r in PROFILE_ROUNDS], a.workload,
+                               kernel_name)
+        pmc = find_profile(a.pmc, [f"{r}_{a.workload}_pmc.json" for r in PROFILE_ROUNDS], a.workload, main_kernel)
+        if rank != 0:
+            return {}, None, violations
         # sanity: the gathered frame holds every pixel's sample count
-        frame_samples = int(frame_cnt.to(torch.int64).sum().item())
-        assert frame_samples == int(samples), (frame_samples, samples)
+        assert int(samples) == int(counted), (samples, counted)
         # the frame the timed steps produced (every step rewrites all of it), against the reference
-        verified, verify_note = verify_frame(a.workload, frame_rgb.view(H, W, 3).cpu().numpy(),
-                                             frame_cnt.view(H, W).cpu().numpy())
-        value = samples * a.steps / elapsed / 1e6
+        ok, verify_note = verify_frame(a.workload, frame_rgb.view(H, W, 3).cpu().numpy(),
+                                       frame_cnt.view(H, W).cpu().numpy())
         work = {"aabb_tests": bbox / samples, "micro_steps": micro / samples, "prim_tests": prim / samples,
                 "queries": queries / samples}
         xwork = {"aabb_tests": x_bbox / samples, "micro_steps": x_micro / samples, "prim_tests": x_prim / samples,
                  "plane_tests": x_plane / samples}
+        more = {
+            "verified": ok,
+            "verify": verify_note,
+            "work_per_sample_reference": work,
+            "work_per_sample_executed": xwork,
+            # run-time audit of the proofs (skipped marches): every 2^AUDIT_EVERY_LOG2-th proven ray
+            # of the untimed executed-work pass re-marched exactly (rrt_set_proof_audit)
+            "proof_violations": violations,
+            "proof_audit": dict(audit, every=1 << AUDIT_EVERY_LOG2),
+        }
+        more.update(rooflines(loc_bytes, ref_bytes, main_ms, kernel_name, main_kernel, traffic, pmc,
+                              out_bytes=float(BYTES_PIXEL * pix_local)))
+        if world == 1 and not a.no_cpu_baseline:
+            threads = a.cpu_threads or host_cores()
+            more["cpu_baseline"] = cpu_baseline(wl, threads, a.cpu_row_stride or wl["row_stride"], scene_path,
+                                                camera_path, env)
+        return more, ok, violations
+
+    full, verified, audit_violations = full_report() if a.full else ({}, None, 0)
+    if rank == 0:
+        value = samples * a.steps / elapsed / 1e6
         out = {
             "metric": "Msamples/sec (whole node), 1080p 64spp CBbunny + Schwarzschild geodesic"
             if a.workload == "cfg3" else f"Msamples/sec (whole node), {wl['desc']}",
@@ -484,25 +547,13 @@ def main():
             "config": {"workload": wl["desc"], "frame": [W, H], "spp": wl["spp"], "tile": tile,
                        "partition": (f"lattice deal of {tile}x{tile} tiles over {world} GPUs, RCCL gather to rank 0"
                                      if world > 1 else "whole frame on 1 GPU, no gather")},
-            "verified": verified,
-            "verify": verify_note,
             "samples_per_frame": int(samples),
             "nominal_msamples_per_s": W * H * wl["spp"] * a.steps / elapsed / 1e6,
             "kernel_ms_rank0": k_ms,
             "main_kernel_ms_rank0": main_ms,
-            "work_per_sample_reference": work,
-            "work_per_sample_executed": xwork,
-            # run-time audit of the proofs (skipped marches): every 2^AUDIT_EVERY_LOG2-th proven ray
-            # of the untimed executed-work pass re-marched exactly (rrt_set_proof_audit)
-            "proof_violations": audit_violations,
-            "proof_audit": dict(audit, every=1 << AUDIT_EVERY_LOG2),
+            "full": bool(a.full),
         }
-        out.update(rooflines(loc_bytes, ref_bytes, main_ms, kernel_name, main_kernel, traffic, pmc,
-                             out_bytes=float(BYTES_PIXEL * pix_local)))
-        if world == 1 and not a.no_cpu_baseline:
-            threads = a.cpu_threads or host_cores()
-            out["cpu_baseline"] = cpu_baseline(wl, threads, a.cpu_row_stride or wl["row_stride"], scene_path,
-                                               camera_path, env)
+        out.update(full)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

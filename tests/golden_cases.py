@@ -1,6 +1,7 @@
 """Golden cases produced by tests/golden/make_golden.py from the reference renderer."""
 import hashlib
 import json
+import lzma
 import os
 import sys
 import tempfile
@@ -32,6 +33,49 @@ def generated_scene(tag, want_dae_sha, want_rrts_sha):
         os.replace(tmp, out)
     with open(out, "rb") as f:
         assert hashlib.sha256(f.read()).hexdigest() == want_rrts_sha, f"{tag}: ingest differs from the reference loader"
+    return out
+
+
+def _dae_bytes(name):
+    """Bytes of the scene asset `name` (no extension) kept under tests/golden/dae/, or None:
+    the file itself, its xz-compressed copy (assets over the size limit for a committed file),
+    or line edits of another asset (variants.json: {name: {"base": asset, "ops": [[i, j, lines]]}},
+    base lines [i, j) replaced by `lines`; the reference ships several near-copies of one mesh)."""
+    d = os.path.join(GOLD, "dae")
+    plain = os.path.join(d, name + ".dae")
+    if os.path.exists(plain):
+        with open(plain, "rb") as f:
+            return f.read()
+    if os.path.exists(plain + ".xz"):
+        with lzma.open(plain + ".xz") as f:
+            return f.read()
+    with open(os.path.join(d, "variants.json")) as f:
+        v = json.load(f).get(name)
+    if v is None:
+        return None
+    lines = _dae_bytes(v["base"]).decode("utf-8").splitlines(keepends=True)
+    for i, j, new in reversed(v["ops"]):
+        lines[i:j] = new
+    return "".join(lines).encode("utf-8")
+
+
+def dae_input(name):
+    """Path of the .dae of the scene asset `name`: the committed file, or one rebuilt from its
+    stored form (_dae_bytes) in the temporary directory; None when the asset is not stored."""
+    plain = os.path.join(GOLD, "dae", name + ".dae")
+    if os.path.exists(plain):
+        return plain
+    data = _dae_bytes(name)
+    if data is None:
+        return None
+    d = os.path.join(tempfile.gettempdir(), "rrt_golden_gen")
+    os.makedirs(d, exist_ok=True)
+    out = os.path.join(d, f"{name}_{hashlib.sha256(data).hexdigest()[:16]}.dae")
+    if not os.path.exists(out):
+        tmp = out + ".tmp%d" % os.getpid()
+        with open(tmp, "wb") as f:
+            f.write(data)
+        os.replace(tmp, out)
     return out
 
 

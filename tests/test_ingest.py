@@ -7,8 +7,8 @@ Camera::configure/place/set_screen_size produce for every scene asset the refere
 (tests/golden/make_ingest_golden.py, oracle harness in dump-only mode).  The ingest must
 reproduce both files byte for byte: vertex order, halfedge vertex normals, triangle order and
 winding, per-object BSDF records, light records and the placed camera.  Inputs: the copies under
-tests/golden/dae/ (input data), or the reference tree for the large assets when it is present.
-No GPU is involved.
+tests/golden/dae/ (input data; golden_cases.dae_input rebuilds the large assets from their stored
+form).  No GPU is involved.
 """
 import hashlib
 import json
@@ -19,21 +19,16 @@ import numpy as np
 import pytest
 
 import rrt
-from golden_cases import GOLD
+from golden_cases import GOLD, dae_input
 
 INGEST = json.load(open(os.path.join(GOLD, "ingest.json")))
-REF_DAE = "/root/reference/pathtracer/dae"
 
 
 def _input(name):
-    e = INGEST[name]
-    local = os.path.join(GOLD, "dae", os.path.basename(e["src"]))
-    if os.path.exists(local):
-        return local
-    ref = os.path.join(REF_DAE, e["src"])
-    if os.path.exists(ref):
-        return ref
-    pytest.skip(f"{name}: input not committed and the reference tree is absent")
+    assert name in INGEST
+    path = dae_input(name)
+    assert path is not None, f"{name}: input not stored under tests/golden/dae/"
+    return path
 
 
 def _sha(path):

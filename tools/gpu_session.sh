@@ -21,11 +21,11 @@ for step in "$@"; do
   case $step in
     test)  run pytest_gpu 900 python3 -u -m pytest tests -m gpu -x -q -s --timeout 300 --timeout-method thread ;;
     smoke) run smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 600 python3 bench.py --steps 5 --warmup 2 ;;
-    bench4) run bench4 600 python3 bench.py --workload cfg4 --steps 2 --warmup 1 ;;
-    bench5) run bench5 900 python3 bench.py --workload cfg5 --steps 1 --warmup 1 ;;
-    bench2) run bench2 600 python3 bench.py --workload cfg2 --steps 5 --warmup 2 ;;
-    benchm3) run benchm3 900 python3 bench.py --workload m3 --steps 2 --warmup 1 ;;
+    bench) run bench 600 python3 bench.py --full --steps 5 --warmup 2 ;;
+    bench4) run bench4 600 python3 bench.py --full --workload cfg4 --steps 2 --warmup 1 ;;
+    bench5) run bench5 900 python3 bench.py --full --workload cfg5 --steps 1 --warmup 1 ;;
+    bench2) run bench2 600 python3 bench.py --full --workload cfg2 --steps 5 --warmup 2 ;;
+    benchm3) run benchm3 900 python3 bench.py --full --workload m3 --steps 2 --warmup 1 ;;
     prof2) run prof2 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof2 -o run --output-format csv -- python3 bench.py --workload cfg2 --steps 5 --warmup 2 --no-cpu-baseline ;;
     profm3) run profm3 900 rocprofv3 --kernel-trace --stats -d gpurun_out/profm3 -o run --output-format csv -- python3 bench.py --workload m3 --steps 2 --warmup 1 --no-cpu-baseline ;;
     traffic) run pmc_fetch 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d gpurun_out/pmc_fetch -o run --output-format csv -- python3 tools/ab_kernels.py --rounds 1 def:0:0
@@ -130,9 +130,9 @@ for step in "$@"; do
              run prof5 900 rocprofv3 --kernel-trace --stats -d gpurun_out/prof5 -o run --output-format csv -- python3 bench.py --workload cfg5 --steps 1 --warmup 1 --no-cpu-baseline &&
              run prof2 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof2 -o run --output-format csv -- python3 bench.py --workload cfg2 --steps 5 --warmup 2 --no-cpu-baseline &&
              run profm3 900 rocprofv3 --kernel-trace --stats -d gpurun_out/profm3 -o run --output-format csv -- python3 bench.py --workload m3 --steps 2 --warmup 1 --no-cpu-baseline ;;
-    benchall) run bench 600 python3 bench.py --steps 5 --warmup 2 && run bench2 600 python3 bench.py --workload cfg2 --steps 5 --warmup 2 &&
-              run bench4 600 python3 bench.py --workload cfg4 --steps 2 --warmup 1 && run bench5 900 python3 bench.py --workload cfg5 --steps 1 --warmup 1 &&
-              run benchm3 900 python3 bench.py --workload m3 --steps 2 --warmup 1 ;;
+    benchall) run bench 600 python3 bench.py --full --steps 5 --warmup 2 && run bench2 600 python3 bench.py --full --workload cfg2 --steps 5 --warmup 2 &&
+              run bench4 600 python3 bench.py --full --workload cfg4 --steps 2 --warmup 1 && run bench5 900 python3 bench.py --full --workload cfg5 --steps 1 --warmup 1 &&
+              run benchm3 900 python3 bench.py --full --workload m3 --steps 2 --warmup 1 ;;
     abfresh) # fresh-pixel continuations for the launch's last claims (cfg3 8-way), rounds 3
            run abfresh 600 python3 tools/ab_workload.py --workload cfg3 --world 8 --rounds 3 0 0:0:RRT_AB_CONT_FRESH=2048 0:0:RRT_AB_CONT_FRESH=8192 0:0:RRT_AB_CONT_FRESH=32768 ;;
     abdeal) # tile deals of the 8-way split: serpentine (lib), serpentine + row offset S (serS), lattice (latS)
