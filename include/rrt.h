@@ -315,6 +315,61 @@ int rrt_partition_tiles(uint32_t frame_w, uint32_t frame_h, uint32_t tile_size, 
 int rrt_region_tiles(uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t tile_size, uint32_t rank,
                      uint32_t world, uint32_t* tiles_out, uint32_t max_tiles);
 
+/* ---------------------------------------------------------------- ray queries
+ * "Where does this ray go?": the geodesic-marched scene query itself, for picking through the
+ * lens of the hole, first-hit buffers, lensing maps and visibility tests.  Replaces: a direct call
+ * of BVHAccel::intersect (bvh.cpp:103-113, with an Intersection, or its boolean for a shadow
+ * query) under the spacetime rrt_set_spacetime installed -- Schwarzschild or Kerr.  Every ray is
+ * marched exactly; no proof is used.  The march is bounded, so any input terminates; a direction
+ * exactly through the hole's centre is degenerate in the reference itself (next_micro_ray divides
+ * by zero and carries NaN): its record is unspecified. */
+typedef struct { double o[3], d[3]; } rrt_ray;   /* 48 bytes; d is used as given (the reference
+                                                    does not normalise it; callers pass unit d) */
+enum { RRT_RAY_MISS = 0,      /* the march ended with neither: the Schwarzschild step count is
+                                 exhausted, or a Kerr escape or budget end */
+       RRT_RAY_HIT = 1,
+       RRT_RAY_CAPTURED = 2 };/* the capture test (bvh.cpp:107; Kerr: the horizon test) fired
+                                 before any hit */
+typedef struct {              /* 96 bytes; without a closest hit every field but status and steps
+                                 is 0, prim and bsdf -1 */
+  double hit_p[3];            /* Intersection::hit_p */
+  double n[3];                /* Intersection::n (triangles: unnormalised, triangle.cpp:47) */
+  double w_out[3];            /* -d of the micro segment that hit */
+  double t;                   /* Intersection::t along that segment */
+  uint32_t status;            /* RRT_RAY_* */
+  int32_t prim;               /* build-order primitive id, as the prims of rrt_get_bvh */
+  int32_t bsdf;               /* index into rrt_scene_desc.bsdfs */
+  uint32_t steps;             /* micro steps taken: index of the hit / capturing segment + 1; on
+                                 a miss, all that were marched */
+} rrt_hit;
+enum { RRT_TRACE_ANY_HIT = 1u << 0 };  /* shadow query: status and steps are the closest-hit
+                                          query's (both return at the first segment with a hit),
+                                          the hit fields stay 0 / -1 */
+enum { RRT_TRACE_AUTO = 0,          /* wave per ray when every ray can hold a resident wave of its
+                                       own at once (Schwarzschild), else lane per ray */
+       RRT_TRACE_LANE_PER_RAY = 1,  /* one lane marches one ray */
+       RRT_TRACE_WAVE_PER_RAY = 2 };/* one wave per ray: 64 micro segments of its chain walked in
+                                       parallel per round; Schwarzschild only:
+                                       RRT_E_INVALID with Kerr.  Records are identical. */
+typedef struct { uint32_t flags, mode, reserved[6]; } rrt_trace_params;  /* NULL = all zero */
+
+/* n rays -> n records.  A scene is needed, no camera.  n == 0 returns RRT_OK without a launch; a
+ * host-only context returns RRT_E_NO_DEVICE.  Device variant: d_rays / d_hits are device
+ * buffers aligned to 16 bytes; asynchronous on `stream`, under the workspace and stream-fence
+ * rules of rrt_render_tiles_device.  Host variant: the library stages the buffers and
+ * synchronises. */
+int rrt_trace_rays_device(rrt_ctx* ctx, const rrt_trace_params* params, const rrt_ray* d_rays, uint32_t n,
+                          rrt_hit* d_hits, void* stream);
+int rrt_trace_rays(rrt_ctx* ctx, const rrt_trace_params* params, const rrt_ray* rays, uint32_t n, rrt_hit* hits);
+/* The pixel-centre camera rays of the region [x0,x0+w) x [y0,y0+h) of a frame_w x frame_h frame,
+ * generated in the kernel: pixel (x, y) takes Camera::generate_ray at ((x + 0.5) / frame_w,
+ * (y + 0.5) / frame_h), as PathTracer::raytrace_pixel with ns_aa == 1 (part1_code.cpp:132-141).
+ * hits: [h][w] row-major over the region, y = 0 at the bottom.  Needs a scene and a camera. */
+int rrt_trace_camera_device(rrt_ctx* ctx, const rrt_trace_params* params, uint32_t frame_w, uint32_t frame_h,
+                            uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, rrt_hit* d_hits, void* stream);
+int rrt_trace_camera(rrt_ctx* ctx, const rrt_trace_params* params, uint32_t frame_w, uint32_t frame_h,
+                     uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, rrt_hit* hits);
+
 /* ---------------------------------------------------------------- introspection */
 typedef struct {
   uint32_t n_prims, n_nodes, n_leaf_refs, max_depth;

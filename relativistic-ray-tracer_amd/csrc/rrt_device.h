@@ -1,5 +1,5 @@
 // rrt_device.h -- device-side restatement of the reference's math, geometry, BSDFs, lights and
-// the geodesic-marched BVH query, shared by the kernels (rrt_kernel.hip, rrt_sample.hip).
+// the geodesic-marched BVH query, shared by the kernels (rrt_kernel.hip, rrt_sample.hip, rrt_query.hip).
 //
 // Numerics follow the reference exactly: double geometry (CGL Vector3D), float Spectrum with
 // the reference's narrowing points, the same operation order, no FMA contraction (the pragma
@@ -271,6 +271,15 @@ __device__ __forceinline__ bool tri_t(const DPrimGeo& gp, v3 o, v3 d, double max
 }
 
 struct Isect { v3 hit_p, w_out, n; int bsdf; };
+// What the ray-query kernels (rrt_query.hip) report beyond the Isect.  segment_walk fills slot and t
+// on a hit; query / kerr_march fill steps and captured.  Every function takes it as a pointer that
+// defaults to null: the render kernels pass none, and with everything inlined their code is unchanged.
+struct QRec {
+  int slot;        // leaf slot of the accepted primitive (closest-hit walks)
+  double t;        // Intersection::t along the segment that hit
+  uint32_t steps;  // micro steps taken: index of the hit / capturing segment + 1; else all marched
+  bool captured;   // the march ended in the capture test (bvh.cpp:107; Kerr: the horizon test)
+};
 
 // BVHAccel::intersect_micro (bvh.cpp:115-138) for one micro segment.  ANY: shadow query, stop
 // at the first accepted primitive (only the boolean is used; result-identical).
@@ -732,7 +741,7 @@ __device__ __forceinline__ void next_micro(const DHole& h, v3& o, v3& d, double&
 // W4: the 4-wide walk may run (query's W4; the Kerr march walks the binary tree only)
 template <bool ANY, bool COUNT, bool W4 = true>
 __device__ __forceinline__ bool segment_walk(const KParams& kp, v3 o, v3 d, double max_t, v3 e, int cell,
-                                             Isect* is, Counters& cn, bool any_rt = false) {
+                                             Isect* is, Counters& cn, bool any_rt = false, QRec* qr = nullptr) {
   // oversized leaves with no primitive within reach of a short segment are not offered
   const uint64_t bmask = (kp.big_mask && cell >= 0 && max_t < kp.big_reach) ? (uint64_t)kp.big_mask[cell] : ~0ull;
   if (!COUNT && kp.diag) {  // diagnostics: skip all / interior-start / exterior-start walks
@@ -767,6 +776,7 @@ __device__ __forceinline__ bool segment_walk(const KParams& kp, v3 o, v3 d, doub
 #endif
   if (COUNT && (kp.diag & 2)) cn.prim = prim_before + (clear_diag ? 0u : cn.bbox - bbox_before);
   if (!hit) return false;
+  if (qr) { qr->slot = slot; qr->t = seg_t; }
   if (!ANY && !any_rt) {
     const DPrimMeta meta = kp.meta[slot];
     is->bsdf = (int)((meta >> 8) & 0xffu);
@@ -786,14 +796,14 @@ __device__ __forceinline__ bool segment_walk(const KParams& kp, v3 o, v3 d, doub
 }
 template <bool ANY, bool COUNT, bool W4 = true>
 __device__ __forceinline__ bool segment_query(const KParams& kp, v3 o, v3 d, double max_t, v3 e, Isect* is,
-                                              Counters& cn, bool any_rt = false) {
+                                              Counters& cn, bool any_rt = false, QRec* qr = nullptr) {
   // e = o + d * max_t.  COUNT && kp.count_exec: count the work this path executes (grid / root
   // skips, clean walk, plane tests in the query slot) instead of the reference's
   const bool opt = !COUNT || kp.count_exec;
   if (opt && segment_outside_root(kp, o, e)) return false;  // root test fails
   const int cell = opt ? grid_cell(kp.grid, o) : -1;
   if (cell_clear(kp.grid, cell, max_t)) return false;  // no primitive within reach
-  return segment_walk<ANY, COUNT, W4>(kp, o, d, max_t, e, cell, is, cn, any_rt);
+  return segment_walk<ANY, COUNT, W4>(kp, o, d, max_t, e, cell, is, cn, any_rt, qr);
 }
 
 // ------------------------------------------------------------------ kernel variants
@@ -970,7 +980,7 @@ __device__ __forceinline__ void audit_note(const KParams& kp, int k, bool violat
 }
 __device__ __forceinline__ bool kerr_occluded_proof(const KParams& kp, v3 o, v3 d);
 template <bool ANY, bool COUNT>
-__device__ __forceinline__ bool kerr_march(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn);
+__device__ __forceinline__ bool kerr_march(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn, QRec* qr = nullptr);
 template <bool ANY, bool COUNT>
 __device__ __forceinline__ bool query_kerr(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn) {
   // shadow rays: the occlusion proof first (never in the reference-work counts)
@@ -985,14 +995,15 @@ __device__ __forceinline__ bool query_kerr(const KParams& kp, v3 o, v3 d, Isect*
 }
 // the march of query_kerr (no proof)
 template <bool ANY, bool COUNT>
-__device__ __forceinline__ bool kerr_march(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn) {
+__device__ __forceinline__ bool kerr_march(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn, QRec* qr) {
   const DHole& h = kp.hole;
   v3 q, p;
   kerr_init(h, o, d, q, p);
   v3 a = o;
   const double rh2 = h.r_hor * h.r_hor;
   double swept = 0.0;
-  for (int j = 0; j < h.kerr_max_steps && swept < 2.0 * PI_D; ++j) {
+  int j = 0;
+  for (; j < h.kerr_max_steps && swept < 2.0 * PI_D; ++j) {
     v3 q1 = q, p1 = p;
     double sw1 = swept;
     KArith<true> fast;
@@ -1002,16 +1013,20 @@ __device__ __forceinline__ bool kerr_march(const KParams& kp, v3 o, v3 d, Isect*
       q1 = q; p1 = p; sw1 = swept;
       escaped = kerr_advance(h, q1, p1, sw1, ieee);
     }
+    if (qr) qr->steps = (uint32_t)j + 1u;  // the step being taken: the one that escapes, captures or hits
     if (escaped) return false;
     q = q1; p = p1; swept = sw1;
     if (COUNT) cn.micro++;
-    if (kerr_r2(h, q) <= rh2) return false;  // captured
+    if (kerr_r2(h, q) <= rh2) {  // captured
+      if (qr) qr->captured = true;
+      return false;
+    }
     const v3 b = kerr_world(h, q);
     const v3 seg = b - a;
     const double max_t = norm(seg);
     const double inv = xdiv(1., max_t);
     const v3 sd = V(seg.x * inv, seg.y * inv, seg.z * inv);  // normalize(seg), norm shared
-    if (segment_query<ANY, COUNT, false>(kp, a, sd, max_t, a + vmul(sd, max_t), is, cn)) return true;
+    if (segment_query<ANY, COUNT, false>(kp, a, sd, max_t, a + vmul(sd, max_t), is, cn, false, qr)) return true;
     a = b;
   }
   return false;
@@ -1256,8 +1271,10 @@ __device__ __forceinline__ bool shadow_occluded_proof(const KParams& kp, v3 o, v
 // walk the binary tree (with the 4-wide walk inlined their scratch grew 2.5-3x: general batch kernel
 // 592 -> 1488 B/lane, Kerr 720 -> 2304 and cfg5 1.41 -> 3.76 s per frame, profiles/r05_ab_kerr_bvh4.txt)
 template <bool ANY, bool COUNT, bool KERR = false, bool W4 = true>
-RRT_QUERY_ATTR bool query(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn, bool any_rt = false) {
-  if (KERR) return query_kerr<ANY, COUNT>(kp, o, d, is, cn);
+RRT_QUERY_ATTR bool query(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn, bool any_rt = false,
+                          QRec* qr = nullptr) {
+  if (KERR) return qr ? kerr_march<ANY, COUNT>(kp, o, d, is, cn, qr) : query_kerr<ANY, COUNT>(kp, o, d, is, cn);
+  if (qr) qr->steps = (uint32_t)kp.hole.steps;  // all marched, unless a segment below ends the march
   if (COUNT && !kp.count_exec && !(kp.diag & 2)) cn.query++;
   RRT_T0(tq0);
   double max_t = 0.0;
@@ -1271,11 +1288,13 @@ RRT_QUERY_ATTR bool query(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn
     if (COUNT) cn.micro++;
     if (sphere_t_rel(rel, rel2, kp.hole.r2, d, max_t)) {  // captured
       RRT_QACC(tq0);
+      if (qr) { qr->steps = (uint32_t)j + 1u; qr->captured = true; }
       return false;
     }
     e = o + vmul(d, max_t);
-    if (segment_query<ANY, COUNT, W4>(kp, o, d, max_t, e, is, cn, any_rt)) {
+    if (segment_query<ANY, COUNT, W4>(kp, o, d, max_t, e, is, cn, any_rt, qr)) {
       RRT_QACC(tq0);
+      if (qr) qr->steps = (uint32_t)j + 1u;
       return true;
     }
   }

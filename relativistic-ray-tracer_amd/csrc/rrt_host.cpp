@@ -35,6 +35,8 @@ hipError_t rrt_launch_first(const KParams& kp, const KParams* d_kp, int lean, in
 hipError_t rrt_launch_pixel_proof(const KParams* d_kp, uint32_t n_pixels, bool strips, hipStream_t stream);
 hipError_t rrt_launch_heavy(const KParams* d_kp, int lean, int waves, int nw, uint32_t grid, int drain, hipStream_t stream);
 hipError_t rrt_launch_path(const KParams* d_kp, int waves, uint32_t grid, hipStream_t stream);
+hipError_t rrt_launch_trace(const KParams* d_kp, const TraceArgs& a, int kerr, int any, int mode, int n_cu, int* mode_out,
+                            hipStream_t stream);
 hipError_t rrt_launch_unpack(const uint32_t* tiles, uint32_t n_tiles, uint32_t ts, uint32_t fw, uint32_t fh,
                              const float* rgb_p, const int32_t* cnt_p, float* rgb, int32_t* cnt, hipStream_t stream);
 hipError_t rrt_launch_libm(int fn, uint64_t n, const double* a, const double* b, double* out, hipStream_t stream);
@@ -171,6 +173,7 @@ struct rrt_ctx {
   DPrimGeo* d_geo = nullptr;
   DPrimNrm* d_nrm = nullptr;
   DPrimMeta* d_meta = nullptr;
+  uint32_t* d_leaf = nullptr;  // leaf slot -> build-order primitive id (the ray queries' rrt_hit.prim)
   DBsdf* d_bsdfs = nullptr;
   DLight* d_lights = nullptr;
   uint8_t* d_grid = nullptr;
@@ -209,6 +212,9 @@ struct rrt_ctx {
   size_t first_cap = 0;
   float* d_rgb = nullptr; int32_t* d_cnt = nullptr; uint32_t* d_draws = nullptr; uint32_t* d_ctr = nullptr;
   size_t px_cap = 0;
+  // host-buffer ray queries (rrt_trace_rays / rrt_trace_camera): staging
+  void* d_trace_rays = nullptr; void* d_trace_hits = nullptr;
+  size_t trace_rays_cap = 0, trace_hits_cap = 0;  // bytes
   float last_ms = 0.f, last_main_ms = 0.f;
   bool timed = false;
   uint32_t last_grid = 0;
@@ -238,6 +244,8 @@ static void free_scene_dev(rrt_ctx* c) {
   hipFree(c->d_nodes); hipFree(c->d_geo); hipFree(c->d_nrm); hipFree(c->d_meta); hipFree(c->d_bsdfs);
   hipFree(c->d_lights); hipFree(c->d_grid); hipFree(c->d_clean); hipFree(c->d_big); hipFree(c->d_planes);
   hipFree(c->d_big_mask);
+  hipFree(c->d_leaf);
+  c->d_leaf = nullptr;
   hipFree(c->d_free);
   c->d_free = nullptr;
   hipFree(c->d_free4);
@@ -314,6 +322,7 @@ void rrt_destroy(rrt_ctx* c) {
     hipFree(c->d_audit);
     hipFree(c->d_cont);
     hipFree(c->d_path_stack);
+    hipFree(c->d_trace_rays); hipFree(c->d_trace_hits);
     for (uint32_t i = 0; i < rrt_ctx::kRing; ++i) {
       if (c->ev0[i]) hipEventDestroy(c->ev0[i]);
       if (c->ev_main[i]) hipEventDestroy(c->ev_main[i]);
@@ -1130,6 +1139,7 @@ extern "C" int rrt_set_scene(rrt_ctx* c, const rrt_scene_desc* s) {
   if ((rc = upload(c, (void**)&c->d_geo, geo.data(), geo.size() * sizeof(DPrimGeo)))) return rc;
   if ((rc = upload(c, (void**)&c->d_nrm, nrm.data(), nrm.size() * sizeof(DPrimNrm)))) return rc;
   if ((rc = upload(c, (void**)&c->d_meta, meta.data(), meta.size() * sizeof(DPrimMeta)))) return rc;
+  if ((rc = upload(c, (void**)&c->d_leaf, c->leaf.data(), c->leaf.size() * sizeof(uint32_t)))) return rc;
   if ((rc = upload(c, (void**)&c->d_bsdfs, c->bsdfs.data(), c->bsdfs.size() * sizeof(DBsdf)))) return rc;
   if ((rc = upload_lights(c))) return rc;
   if (!c->grid.empty() && (rc = upload(c, (void**)&c->d_grid, c->grid.data(), c->grid.size()))) return rc;
@@ -1342,6 +1352,65 @@ extern "C" int rrt_proof_envelope(const rrt_ctx* c) {
   return in_proof_envelope(c) ? 1 : 0;
 }
 
+// The scene, walk hierarchy, camera and hole of a launch's KParams: what every kernel that runs a
+// query needs (the render launches below and the ray queries, rrt_trace).  flags: RRT_RENDER_*
+// (the walk's A/B switches).
+static void fill_scene_params(const rrt_ctx* c, uint32_t flags, KParams& kp) {
+  kp.nodes = c->d_nodes; kp.geo = c->d_geo; kp.nrm = c->d_nrm; kp.meta = c->d_meta;
+  kp.bsdfs = c->d_bsdfs; kp.lights = c->d_lights; kp.n_lights = (uint32_t)c->lights.size() + (c->env_w ? 1u : 0u);
+  kp.env.tex = c->d_env_tex; kp.env.pdf = c->d_env_pdf; kp.env.conds = c->d_env_conds; kp.env.marg = c->d_env_marg;
+  kp.env.w = c->env_w; kp.env.h = c->env_h;
+  kp.fast_div = (c->fast_div && !(flags & RRT_RENDER_EXACT_DIV)) ? 1u : 0u;
+  kp.cam = c->cam; kp.hole = c->hole;
+  kp.grid = c->hgrid;
+  kp.grid.k = (flags & RRT_RENDER_NO_SKIP) ? nullptr : c->d_grid;
+  // the walk always runs over a "clean" tree: the real one, or the reference tree (whose DNode
+  // pad carries the first-leaf ordinals too) with an empty oversized-leaf list
+  const bool use_clean = c->has_clean && !(flags & RRT_RENDER_NO_CLEAN);
+  kp.clean_nodes = use_clean ? c->d_clean : c->d_nodes;
+  kp.big = c->d_big; kp.clean_root = 0; kp.n_big = use_clean ? c->n_big : 0u;
+  kp.big_mask = (use_clean && !(flags & RRT_RENDER_NO_SKIP)) ? c->d_big_mask : nullptr;
+  kp.big_reach = (RRT_BIG_REACH - 1) * c->hgrid.h_free;
+  kp.free_big_mask = ~0ull;
+  // the walk's hierarchy (rrt_device.h traverse_free): the SAH search tree by default; for A/B
+  // the clean tree (RRT_RENDER_NO_SEARCH_TREE) or the reference tree itself (RRT_RENDER_NO_CLEAN,
+  // no oversized list) -- every one of them holds the reference's leaves, so results are equal
+  {
+    const bool no_search = (flags & RRT_RENDER_NO_SEARCH_TREE) || !c->d_free;
+    if ((flags & RRT_RENDER_NO_CLEAN) || (!c->has_clean && no_search)) {
+      kp.free_nodes = c->d_nodes; kp.n_big = 0;
+    } else if (no_search) {
+      kp.free_nodes = c->d_clean;
+    } else {
+      kp.free_nodes = c->d_free;  // over the clean tree's leaves (+ kp.big), or every leaf
+      kp.free_big_mask = c->free_big_mask;
+      // the 4-wide walk of the same tree (A/B: RRT_AB_NO_BVH4=1 in the environment)
+      const char* nb4 = std::getenv("RRT_AB_NO_BVH4");
+      kp.free4 = (nb4 && nb4[0] == '1') ? nullptr : c->d_free4;
+      kp.free4_omax = c->free4_omax;
+    }
+  }
+  kp.planes = c->d_planes; kp.plane_eps = c->plane_eps;
+  {
+    const Box& rb = c->nodes[0].bb;
+    const double lo[3] = {rb.mn.x, rb.mn.y, rb.mn.z}, hi[3] = {rb.mx.x, rb.mx.y, rb.mx.z};
+    const bool ok = c->plane_eps > 0 && !(flags & RRT_RENDER_NO_SKIP);
+    for (int k = 0; k < 3; ++k) {  // no skip: an empty test range (-inf, +inf)
+      kp.root_lo[k] = ok ? lo[k] - c->plane_eps : -INFINITY;
+      kp.root_hi[k] = ok ? hi[k] + c->plane_eps : INFINITY;
+    }
+    // Kerr escape radius (DESIGN.md §10): the farthest root-box corner from the hole, >= 4M
+    double m3[3];
+    for (int k = 0; k < 3; ++k) {
+      const double dl = std::fabs(lo[k] - kp.hole.c[k]), dh = std::fabs(hi[k] - kp.hole.c[k]);
+      m3[k] = dl > dh ? dl : dh;
+    }
+    const double e2 = (m3[0] * m3[0] + m3[1] * m3[1]) + m3[2] * m3[2], f2 = (4.0 * kp.hole.m) * (4.0 * kp.hole.m);
+    kp.hole.r_esc2 = e2 > f2 ? e2 : f2;
+    kp.hole.kerr_max_steps = 4 * kp.hole.steps;
+  }
+}
+
 static int launch(rrt_ctx* c, const rrt_render_params* p, const uint32_t* tiles, uint32_t n_tiles, uint32_t ts,
                   uint32_t cx0, uint32_t cy0, uint32_t cx1, uint32_t cy1, float* d_rgb, int32_t* d_cnt,
                   uint32_t* d_draws, uint32_t* d_ctr, hipStream_t stream) {
@@ -1380,59 +1449,7 @@ static int launch(rrt_ctx* c, const rrt_render_params* p, const uint32_t* tiles,
   HIPCHK(c, hipMemcpyAsync(c->d_tiles, tiles, sizeof(uint32_t) * 2 * n_tiles, hipMemcpyHostToDevice, stream));
   HIPCHK(c, hipMemsetAsync(c->d_counter, 0, kCounterBytes, stream));
   KParams kp{};
-  kp.nodes = c->d_nodes; kp.geo = c->d_geo; kp.nrm = c->d_nrm; kp.meta = c->d_meta;
-  kp.bsdfs = c->d_bsdfs; kp.lights = c->d_lights; kp.n_lights = (uint32_t)c->lights.size() + (c->env_w ? 1u : 0u);
-  kp.env.tex = c->d_env_tex; kp.env.pdf = c->d_env_pdf; kp.env.conds = c->d_env_conds; kp.env.marg = c->d_env_marg;
-  kp.env.w = c->env_w; kp.env.h = c->env_h;
-  kp.fast_div = (c->fast_div && !(p->flags & RRT_RENDER_EXACT_DIV)) ? 1u : 0u;
-  kp.cam = c->cam; kp.hole = c->hole;
-  kp.grid = c->hgrid;
-  kp.grid.k = (p->flags & RRT_RENDER_NO_SKIP) ? nullptr : c->d_grid;
-  // the walk always runs over a "clean" tree: the real one, or the reference tree (whose DNode
-  // pad carries the first-leaf ordinals too) with an empty oversized-leaf list
-  const bool use_clean = c->has_clean && !(p->flags & RRT_RENDER_NO_CLEAN);
-  kp.clean_nodes = use_clean ? c->d_clean : c->d_nodes;
-  kp.big = c->d_big; kp.clean_root = 0; kp.n_big = use_clean ? c->n_big : 0u;
-  kp.big_mask = (use_clean && !(p->flags & RRT_RENDER_NO_SKIP)) ? c->d_big_mask : nullptr;
-  kp.big_reach = (RRT_BIG_REACH - 1) * c->hgrid.h_free;
-  kp.free_big_mask = ~0ull;
-  // the walk's hierarchy (rrt_device.h traverse_free): the SAH search tree by default; for A/B
-  // the clean tree (RRT_RENDER_NO_SEARCH_TREE) or the reference tree itself (RRT_RENDER_NO_CLEAN,
-  // no oversized list) -- every one of them holds the reference's leaves, so results are equal
-  {
-    const bool no_search = (p->flags & RRT_RENDER_NO_SEARCH_TREE) || !c->d_free;
-    if ((p->flags & RRT_RENDER_NO_CLEAN) || (!c->has_clean && no_search)) {
-      kp.free_nodes = c->d_nodes; kp.n_big = 0;
-    } else if (no_search) {
-      kp.free_nodes = c->d_clean;
-    } else {
-      kp.free_nodes = c->d_free;  // over the clean tree's leaves (+ kp.big), or every leaf
-      kp.free_big_mask = c->free_big_mask;
-      // the 4-wide walk of the same tree (A/B: RRT_AB_NO_BVH4=1 in the environment)
-      const char* nb4 = std::getenv("RRT_AB_NO_BVH4");
-      kp.free4 = (nb4 && nb4[0] == '1') ? nullptr : c->d_free4;
-      kp.free4_omax = c->free4_omax;
-    }
-  }
-  kp.planes = c->d_planes; kp.plane_eps = c->plane_eps;
-  {
-    const Box& rb = c->nodes[0].bb;
-    const double lo[3] = {rb.mn.x, rb.mn.y, rb.mn.z}, hi[3] = {rb.mx.x, rb.mx.y, rb.mx.z};
-    const bool ok = c->plane_eps > 0 && !(p->flags & RRT_RENDER_NO_SKIP);
-    for (int k = 0; k < 3; ++k) {  // no skip: an empty test range (-inf, +inf)
-      kp.root_lo[k] = ok ? lo[k] - c->plane_eps : -INFINITY;
-      kp.root_hi[k] = ok ? hi[k] + c->plane_eps : INFINITY;
-    }
-    // Kerr escape radius (DESIGN.md §10): the farthest root-box corner from the hole, >= 4M
-    double m3[3];
-    for (int k = 0; k < 3; ++k) {
-      const double dl = std::fabs(lo[k] - kp.hole.c[k]), dh = std::fabs(hi[k] - kp.hole.c[k]);
-      m3[k] = dl > dh ? dl : dh;
-    }
-    const double e2 = (m3[0] * m3[0] + m3[1] * m3[1]) + m3[2] * m3[2], f2 = (4.0 * kp.hole.m) * (4.0 * kp.hole.m);
-    kp.hole.r_esc2 = e2 > f2 ? e2 : f2;
-    kp.hole.kerr_max_steps = 4 * kp.hole.steps;
-  }
+  fill_scene_params(c, p->flags, kp);
   bool proofs_valid = false;
   {  // camera-ray miss proof constants (rrt_device.h camera_miss_proof)
     const DHole& h = kp.hole;
@@ -2051,6 +2068,118 @@ extern "C" int rrt_libm_eval(rrt_ctx* c, int fn, const double* a, const double* 
   HIPCHK(c, rrt_launch_libm(fn, n, da, db, dout, (hipStream_t)0));
   HIPCHK(c, hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
   return RRT_OK;
+}
+
+// ---------------------------------------------------------------- ray queries (rrt_query.hip)
+// One launch of the ray-query kernels: n caller rays (d_rays) or, with cam, the pixel-centre
+// camera rays of the region (x0, y0, w, n / w) of a fw x fh frame.  The context's workspace holds the
+// launch's KParams, so the fence rules are the render launches'.
+static int trace_launch(rrt_ctx* c, const rrt_trace_params* tp, bool cam, const rrt_ray* d_rays, uint32_t fw, uint32_t fh,
+                        uint32_t x0, uint32_t y0, uint32_t w, uint32_t n, rrt_hit* d_hits, hipStream_t stream) {
+  static_assert(sizeof(rrt_ray) == 48 && sizeof(rrt_hit) == 96, "rrt_ray / rrt_hit layout (rrt_query.hip stores)");
+  const uint32_t flags = tp ? tp->flags : 0u, mode = tp ? tp->mode : (uint32_t)RRT_TRACE_AUTO;
+  if (flags & ~(uint32_t)RRT_TRACE_ANY_HIT) return fail(c, RRT_E_INVALID, "unknown rrt_trace_params flags");
+  if (mode > RRT_TRACE_WAVE_PER_RAY) return fail(c, RRT_E_INVALID, "unknown rrt_trace_params mode");
+  if (!c->has_scene) return fail(c, RRT_E_INVALID, "no scene (rrt_set_scene)");
+  if (cam && !c->has_camera) return fail(c, RRT_E_INVALID, "no camera (rrt_set_camera)");
+  const bool kerr = c->hole.kind == RRT_METRIC_KERR;
+  if (kerr && mode == RRT_TRACE_WAVE_PER_RAY)
+    return fail(c, RRT_E_INVALID, "RRT_TRACE_WAVE_PER_RAY walks the Schwarzschild stepper's chain only (Kerr: lane per ray)");
+  if (c->device < 0) return fail(c, RRT_E_NO_DEVICE, "host-only context cannot trace");
+  if (n == 0) return RRT_OK;
+  if (!d_hits || (!cam && !d_rays)) return fail(c, RRT_E_INVALID, "null argument");
+  if (((uintptr_t)d_rays | (uintptr_t)d_hits) & 15u) return fail(c, RRT_E_INVALID, "ray / hit buffers must be 16-byte aligned");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = scratch_acquire(c, stream)) return rc;
+  struct FenceGuard {
+    rrt_ctx* c; hipStream_t s;
+    ~FenceGuard() { scratch_release(c, s); }
+  } fence_guard{c, stream};
+  KParams kp{};  // proofs, audit, diagnostics and render state: all off / unused
+  fill_scene_params(c, 0u, kp);
+  kp.frame_w = (double)fw; kp.frame_h = (double)fh;
+  kp.frame_wi = fw; kp.frame_hi = fh;
+  HIPCHK(c, hipMemcpyAsync(c->d_kp, &kp, sizeof(KParams), hipMemcpyHostToDevice, stream));
+  TraceArgs a{};
+  a.rays = cam ? nullptr : reinterpret_cast<const double*>(d_rays);
+  a.hits = d_hits;
+  a.slot_prim = c->d_leaf;
+  a.n = n; a.x0 = x0; a.y0 = y0; a.w = w ? w : 1u;
+  HIPCHK(c, rrt_launch_trace(c->d_kp, a, kerr ? 1 : 0, (flags & RRT_TRACE_ANY_HIT) ? 1 : 0, (int)mode, c->n_cu, nullptr,
+                             stream));
+  return RRT_OK;
+}
+
+// a camera region's ray count, or a failure
+static int trace_region(rrt_ctx* c, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t* n) {
+  *n = 0;
+  if (w == 0 || h == 0) return RRT_OK;
+  if (fw == 0 || fh == 0) return fail(c, RRT_E_INVALID, "frame size is zero");
+  if ((uint64_t)x0 + w > fw || (uint64_t)y0 + h > fh) return fail(c, RRT_E_INVALID, "region outside frame");
+  if ((uint64_t)w * h > 0xffffffffull) return fail(c, RRT_E_INVALID, "region of more than 2^32 - 1 pixels");
+  *n = w * h;
+  return RRT_OK;
+}
+
+// staging buffer of a host-buffer query (grown as needed; hipFree waits for the device)
+static int trace_stage(rrt_ctx* c, void** p, size_t& cap, size_t bytes) {
+  if (cap >= bytes) return RRT_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  hipFree(*p); *p = nullptr; cap = 0;
+  HIPCHK(c, hipMalloc(p, bytes));
+  cap = bytes;
+  return RRT_OK;
+}
+
+extern "C" int rrt_trace_rays_device(rrt_ctx* c, const rrt_trace_params* tp, const rrt_ray* d_rays, uint32_t n,
+                                     rrt_hit* d_hits, void* stream) {
+  if (!c) return RRT_E_INVALID;
+  return trace_launch(c, tp, false, d_rays, 0, 0, 0, 0, 0, n, d_hits, stream ? (hipStream_t)stream : (hipStream_t)0);
+}
+
+extern "C" int rrt_trace_camera_device(rrt_ctx* c, const rrt_trace_params* tp, uint32_t fw, uint32_t fh, uint32_t x0,
+                                       uint32_t y0, uint32_t w, uint32_t h, rrt_hit* d_hits, void* stream) {
+  if (!c) return RRT_E_INVALID;
+  uint32_t n = 0;
+  if (int rc = trace_region(c, fw, fh, x0, y0, w, h, &n)) return rc;
+  return trace_launch(c, tp, true, nullptr, fw, fh, x0, y0, w, n, d_hits, stream ? (hipStream_t)stream : (hipStream_t)0);
+}
+
+// the host-buffer forms: stage, launch on the context's stream, copy back, synchronise
+static int trace_host(rrt_ctx* c, const rrt_trace_params* tp, bool cam, const rrt_ray* rays, uint32_t fw, uint32_t fh, uint32_t x0,
+                      uint32_t y0, uint32_t w, uint32_t n, rrt_hit* hits) {
+  const bool staged = n && c->device >= 0 && c->has_scene;
+  if (staged) {
+    if (int rc = trace_stage(c, &c->d_trace_hits, c->trace_hits_cap, sizeof(rrt_hit) * (size_t)n)) return rc;
+    if (!cam) {
+      if (int rc = trace_stage(c, &c->d_trace_rays, c->trace_rays_cap, sizeof(rrt_ray) * (size_t)n)) return rc;
+      // (every host-buffer query ends in the synchronise below: no earlier one still reads the staging)
+      HIPCHK(c, hipMemcpyAsync(c->d_trace_rays, rays, sizeof(rrt_ray) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    }
+  }
+  // not staged: a call that fails or has nothing to do (trace_launch says which) before any buffer is used
+  if (int rc = trace_launch(c, tp, cam, staged && !cam ? (const rrt_ray*)c->d_trace_rays : nullptr, fw, fh, x0, y0, w, n,
+                            staged ? (rrt_hit*)c->d_trace_hits : nullptr, c->stream))
+    return rc;
+  if (!staged) return RRT_OK;
+  HIPCHK(c, hipMemcpyAsync(hits, c->d_trace_hits, sizeof(rrt_hit) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return RRT_OK;
+}
+
+extern "C" int rrt_trace_rays(rrt_ctx* c, const rrt_trace_params* tp, const rrt_ray* rays, uint32_t n, rrt_hit* hits) {
+  if (!c) return RRT_E_INVALID;
+  if (n && (!rays || !hits)) return fail(c, RRT_E_INVALID, "null argument");
+  return trace_host(c, tp, false, rays, 0, 0, 0, 0, 0, n, hits);
+}
+
+extern "C" int rrt_trace_camera(rrt_ctx* c, const rrt_trace_params* tp, uint32_t fw, uint32_t fh, uint32_t x0, uint32_t y0,
+                                uint32_t w, uint32_t h, rrt_hit* hits) {
+  if (!c) return RRT_E_INVALID;
+  uint32_t n = 0;
+  if (int rc = trace_region(c, fw, fh, x0, y0, w, h, &n)) return rc;
+  if (n && !hits) return fail(c, RRT_E_INVALID, "null argument");
+  return trace_host(c, tp, true, nullptr, fw, fh, x0, y0, w, n, hits);
 }
 
 extern "C" int rrt_render(rrt_ctx* c, const rrt_render_params* p, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,

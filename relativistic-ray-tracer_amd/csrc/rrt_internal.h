@@ -308,5 +308,14 @@ struct KParams {
   uint32_t* wd;
 #endif
 };
+// One launch of the ray-query kernels (rrt_query.hip), passed by value beside the KParams (which
+// carry the scene, the hole and, for camera rays, the camera and the frame size).
+struct TraceArgs {
+  const double* rays;        // [n] rrt_ray (o, d), 16-byte aligned; null: camera rays
+  void* hits;                // [n] rrt_hit, 16-byte aligned
+  const uint32_t* slot_prim; // leaf slot -> build-order primitive id (rrt_get_bvh's prims)
+  uint32_t n;
+  uint32_t x0, y0, w;        // camera rays: ray i is pixel (x0 + i % w, y0 + i / w)
+};
 #define RRT_WD_WORDS (1u << 18)
 #define RRT_WD_HEAVY (1u << 17)

@@ -1,0 +1,169 @@
+// rrt_query.hip -- batched geodesic ray queries (rrt_trace_rays / rrt_trace_camera, include/rrt.h):
+// BVHAccel::intersect (bvh.cpp:103-113) for caller-given rays or the camera's pixel-centre rays,
+// one rrt_hit record per ray instead of a pixel.  Every ray is marched exactly (no proofs); the
+// walks take query's result-neutral accelerations (empty-space grid, search tree).
+//
+// Two decompositions, bit-identical records:
+//   * lane per ray (both metrics): block b takes rays [256 b, 256 b + 256), one lane each, the
+//     render kernels' query() / kerr_march() with the out-record (rrt_device.h QRec);
+//   * wave per ray (Schwarzschild): a ray's micro-ray chain does not depend on any BVH result
+//     (bvh.cpp:105-110, blackhole.cpp:17-40), so the wave produces 64 segments of the chain first
+//     -- every lane steps the same chain, lane l keeps segment 64 r + l -- and then each lane walks
+//     its own segment.  Every segment's closest hit starts from max_t = its own length whatever
+//     came before (bvh.cpp:104-110), and the reference returns at the first segment with a capture
+//     or a hit, so the lowest flagged lane holds the reference's answer.  No LDS, no barrier, no
+//     traffic between waves.
+// No claim counter, no spin, no wait on another block or kernel: the grid is sized from n.
+#include "rrt_device.h"
+
+namespace rrt {
+
+// ray i of the launch: the caller's (three 16-byte loads of the 48-byte rrt_ray), or pixel i's
+// centre ray as raytrace_pixel generates it with ns_aa == 1 (part1_code.cpp:132-141, 182-187)
+template <bool CAM>
+__device__ __forceinline__ void load_ray(const KParams& kp, const TraceArgs& a, uint32_t i, v3& o, v3& d) {
+  if (CAM) {
+    const uint32_t x = a.x0 + i % a.w, y = a.y0 + i / a.w;
+    o = ld3(kp.cam.pos);
+    d = pixel_ray_dir(kp, (double)x + 0.5, (double)y + 0.5);
+  } else {
+    const double2* p = reinterpret_cast<const double2*>(a.rays) + 3 * (size_t)i;
+    const double2 q0 = p[0], q1 = p[1], q2 = p[2];
+    o = V(q0.x, q0.y, q1.x);
+    d = V(q1.y, q2.x, q2.y);
+  }
+}
+
+// the 96-byte rrt_hit of ray i as six 16-byte stores; full: a closest-hit record (is, qr.slot, qr.t),
+// else every hit field is 0 / -1
+__device__ __forceinline__ void store_hit(const TraceArgs& a, uint32_t i, uint32_t status, uint32_t steps, bool full,
+                                          const Isect& is, const QRec& qr) {
+  double2* h = reinterpret_cast<double2*>(a.hits) + 6 * (size_t)i;
+  uint4 tail;
+  tail.x = status; tail.y = 0xffffffffu; tail.z = 0xffffffffu; tail.w = steps;
+  if (full) {
+    h[0] = make_double2(is.hit_p.x, is.hit_p.y);
+    h[1] = make_double2(is.hit_p.z, is.n.x);
+    h[2] = make_double2(is.n.y, is.n.z);
+    h[3] = make_double2(is.w_out.x, is.w_out.y);
+    h[4] = make_double2(is.w_out.z, qr.t);
+    tail.y = a.slot_prim[qr.slot];
+    tail.z = (uint32_t)is.bsdf;
+  } else {
+    const double2 z = make_double2(0.0, 0.0);
+    h[0] = z; h[1] = z; h[2] = z; h[3] = z; h[4] = z;
+  }
+  *reinterpret_cast<uint4*>(h + 5) = tail;
+}
+
+}  // namespace rrt
+
+// KERR: the Kerr march; ANY: shadow query (RRT_TRACE_ANY_HIT); CAM: camera rays
+template <bool KERR, bool ANY, bool CAM>
+__global__ __launch_bounds__(256) void rrt_trace_lane_kernel(const KParams* __restrict__ kpp, const TraceArgs a) {
+  using namespace rrt;
+  const KParams& kp = *kpp;
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= a.n) return;
+  v3 o, d;
+  load_ray<CAM>(kp, a, i, o, d);
+  Isect is;
+  QRec qr = {-1, 0.0, 0u, false};
+  Counters cn = {};
+  const bool hit = KERR ? kerr_march<ANY, false>(kp, o, d, &is, cn, &qr)
+                        : query<ANY, false, false, true>(kp, o, d, &is, cn, false, &qr);
+  store_hit(a, i, hit ? RRT_RAY_HIT : qr.captured ? RRT_RAY_CAPTURED : RRT_RAY_MISS, qr.steps, hit && !ANY, is, qr);
+}
+
+// Schwarzschild; block b takes rays [4 b, 4 b + 4), one wave each
+template <bool ANY, bool CAM>
+__global__ __launch_bounds__(256) void rrt_trace_wave_kernel(const KParams* __restrict__ kpp, const TraceArgs a) {
+  using namespace rrt;
+  const KParams& kp = *kpp;
+  const int lane = (int)(threadIdx.x & 63u);
+  const uint32_t i = blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (i >= a.n) return;  // the whole wave
+  v3 o, d;
+  load_ray<CAM>(kp, a, i, o, d);
+  double max_t = 0.0;
+  v3 e = o + vmul(d, max_t);  // micro = Ray(o, d, max_t = 0), bvh.cpp:104
+  Isect is;
+  QRec qr = {-1, 0.0, 0u, false};
+  Counters cn = {};
+  const int steps = kp.hole.steps;
+  for (int base = 0; base < steps; base += 64) {
+    // 1. the round's stretch of the chain, the same values in every lane (query()'s operations in
+    // query()'s order); lane l keeps segment base + l; the chain stops at the first capture
+    const int n_round = steps - base < 64 ? steps - base : 64;
+    v3 so = o, sd = d, se = e;
+    double smt = max_t;
+    int cap = -1;
+    for (int l = 0; l < n_round; ++l) {
+      v3 rel;
+      double rel2;
+      next_micro_at(kp.hole, e, o, d, max_t, rel, rel2);
+      // wave-uniform by construction: taken from the first lane, so the branch is a scalar one
+      const bool c = __builtin_amdgcn_readfirstlane((int)sphere_t_rel(rel, rel2, kp.hole.r2, d, max_t)) != 0;
+      e = o + vmul(d, max_t);
+      if (lane == l) { so = o; sd = d; smt = max_t; se = e; }
+      if (c) { cap = l; break; }
+    }
+    // 2. each lane below the capture walks its own segment: its full closest hit (or any hit)
+    const int n_seg = cap >= 0 ? cap : n_round;
+    bool hit = false;
+    if (lane < n_seg) hit = segment_query<ANY, false, true>(kp, so, sd, smt, se, &is, cn, false, &qr);
+    // 3. the lowest flagged segment is where the reference's march returns
+    const bool captured = lane == cap;
+    const uint64_t flagged = __ballot(hit || captured);
+    if (flagged) {
+      if (lane == __ffsll((unsigned long long)flagged) - 1)
+        store_hit(a, i, captured ? RRT_RAY_CAPTURED : RRT_RAY_HIT, (uint32_t)(base + lane) + 1u, hit && !ANY, is, qr);
+      return;
+    }
+    // 4. none: the next round continues from the chain's state (o, d, max_t, e)
+  }
+  if (lane == 0) store_hit(a, i, RRT_RAY_MISS, (uint32_t)steps, false, is, qr);
+}
+
+// ------------------------------------------------------------------ launch shim (C++ linkage)
+// mode: RRT_TRACE_*; AUTO takes wave-per-ray when every ray can hold a resident wave of its own at
+// once -- n <= CUs x the wave kernel's resident waves per CU -- since below that count lane-per-ray
+// could not fill the machine anyway (Schwarzschild only; DESIGN.md §5 has the measured crossing).
+// *mode_out: the mode launched.
+hipError_t rrt_launch_trace(const KParams* d_kp, const TraceArgs& a, int kerr, int any, int mode, int n_cu, int* mode_out,
+                            hipStream_t stream) {
+  const bool cam = a.rays == nullptr;
+#define RRT_WAVE_K(A, C) rrt_trace_wave_kernel<A, C>
+#define RRT_PICK(F, ...)                                          \
+  do {                                                            \
+    if (any) { if (cam) F(true, true, ##__VA_ARGS__); else F(true, false, ##__VA_ARGS__); } \
+    else     { if (cam) F(false, true, ##__VA_ARGS__); else F(false, false, ##__VA_ARGS__); } \
+  } while (0)
+  if (mode == RRT_TRACE_AUTO) {
+    mode = RRT_TRACE_LANE_PER_RAY;
+    if (!kerr) {
+      int blocks = 0;
+      hipError_t e = hipSuccess;
+#define RRT_OCC(A, C) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, RRT_WAVE_K(A, C), 256, 0)
+      RRT_PICK(RRT_OCC);
+#undef RRT_OCC
+      if (e != hipSuccess) return e;
+      if ((uint64_t)a.n <= (uint64_t)n_cu * 4u * (uint64_t)blocks) mode = RRT_TRACE_WAVE_PER_RAY;
+    }
+  }
+  if (mode_out) *mode_out = mode;
+  if (mode == RRT_TRACE_WAVE_PER_RAY) {
+    const uint32_t grid = (a.n - 1u) / 4u + 1u;  // n > 0
+#define RRT_GO(A, C) hipLaunchKernelGGL((RRT_WAVE_K(A, C)), dim3(grid), dim3(256), 0, stream, d_kp, a)
+    RRT_PICK(RRT_GO);
+#undef RRT_GO
+  } else {
+    const uint32_t grid = (a.n - 1u) / 256u + 1u;
+#define RRT_GO(A, C, K) hipLaunchKernelGGL((rrt_trace_lane_kernel<K, A, C>), dim3(grid), dim3(256), 0, stream, d_kp, a)
+    if (kerr) RRT_PICK(RRT_GO, true); else RRT_PICK(RRT_GO, false);
+#undef RRT_GO
+  }
+#undef RRT_PICK
+#undef RRT_WAVE_K
+  return hipGetLastError();
+}

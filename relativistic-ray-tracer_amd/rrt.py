@@ -10,6 +10,7 @@ Reference correspondence (pathtracer.h / pathtracer.cpp):
     .set_camera(camera)               PathTracer::set_camera (:119-134)
     .set_black_hole(c, r_s, dtheta)   the `-B` override of global_black_hole (main.cpp:139-145)
     .render(params, x0, y0, w, h)     raytrace_tile / raytrace_cell over a region (:549-609)
+    .trace_rays(o, d) / .trace_camera BVHAccel::intersect itself, one first-hit record per ray (bvh.cpp:103-113)
     RenderParams(...)                 AppConfig fields (application.h:41-85)
 """
 import ctypes as C
@@ -98,6 +99,27 @@ class Stats(C.Structure):
                 ("last_heavy_pixels", C.c_uint32), ("last_cont_pixels", C.c_uint32)]
 
 
+# ray queries (include/rrt.h "ray queries")
+RRT_RAY_MISS, RRT_RAY_HIT, RRT_RAY_CAPTURED = 0, 1, 2
+RRT_TRACE_ANY_HIT = 1
+RRT_TRACE_AUTO, RRT_TRACE_LANE_PER_RAY, RRT_TRACE_WAVE_PER_RAY = 0, 1, 2
+TRACE_MODES = {"auto": RRT_TRACE_AUTO, "lane": RRT_TRACE_LANE_PER_RAY, "wave": RRT_TRACE_WAVE_PER_RAY}
+RAY_DTYPE = np.dtype([("o", np.float64, 3), ("d", np.float64, 3)])  # rrt_ray, 48 bytes
+HIT_DTYPE = np.dtype([("hit_p", np.float64, 3), ("n", np.float64, 3), ("w_out", np.float64, 3), ("t", np.float64),
+                      ("status", np.uint32), ("prim", np.int32), ("bsdf", np.int32), ("steps", np.uint32)])  # rrt_hit, 96
+
+
+class TraceParams(C.Structure):  # rrt_trace_params
+    _fields_ = [("flags", C.c_uint32), ("mode", C.c_uint32), ("reserved", C.c_uint32 * 6)]
+
+
+def trace_params(any_hit=False, mode="auto"):
+    p = TraceParams()
+    p.flags = RRT_TRACE_ANY_HIT if any_hit else 0
+    p.mode = TRACE_MODES[mode] if isinstance(mode, str) else int(mode)
+    return p
+
+
 # every symbol include/rrt.h declares (checked by tests/test_capi_host.py)
 EXPORTS = ["rrt_abi_version", "rrt_create", "rrt_destroy", "rrt_last_error", "rrt_set_scene", "rrt_set_camera",
            "rrt_set_spacetime", "rrt_render_params_default", "rrt_render", "rrt_render_tiles_device",
@@ -108,7 +130,8 @@ EXPORTS = ["rrt_abi_version", "rrt_create", "rrt_destroy", "rrt_last_error", "rr
            "rrt_camera_state_desc", "rrt_set_envmap", "rrt_tonemap_pixel", "rrt_write_png",
            "rrt_exr_load", "rrt_exr_free", "rrt_exr_save", "rrt_kerr_frame", "rrt_get_big_masks",
            "rrt_get_occluders", "rrt_group_create", "rrt_group_render", "rrt_group_destroy", "rrt_libm_eval",
-           "rrt_set_proof_audit", "rrt_get_proof_audit", "rrt_get_search_tree4"]
+           "rrt_set_proof_audit", "rrt_get_proof_audit", "rrt_get_search_tree4", "rrt_trace_rays",
+           "rrt_trace_rays_device", "rrt_trace_camera", "rrt_trace_camera_device"]
 AUDIT_KINDS = ("camera", "shadow", "pixel", "strip", "kerr", "zero")  # include/rrt.h RRT_AUDIT_*
 
 _lib = None
@@ -162,6 +185,12 @@ def lib():
             L.rrt_set_proof_audit.argtypes = [vp, C.c_int]
             L.rrt_get_proof_audit.argtypes = [vp, vp]
         L.rrt_proof_envelope.argtypes = [vp]
+        if hasattr(L, "rrt_trace_rays"):  # absent from older builds loaded through RRT_LIB
+            tp = C.POINTER(TraceParams)
+            L.rrt_trace_rays.argtypes = [vp, tp, vp, C.c_uint32, vp]
+            L.rrt_trace_rays_device.argtypes = [vp, tp, vp, C.c_uint32, vp, vp]
+            L.rrt_trace_camera.argtypes = [vp, tp] + [C.c_uint32] * 6 + [vp]
+            L.rrt_trace_camera_device.argtypes = [vp, tp] + [C.c_uint32] * 6 + [vp, vp]
         L.rrt_get_bvh.argtypes = [vp, vp, vp, vp]
         for name, n_args in (("rrt_get_free_grid", 4), ("rrt_get_clean_tree", 5), ("rrt_get_search_tree", 3),
                              ("rrt_get_search_tree4", 3),
@@ -437,6 +466,37 @@ class Renderer:
 
     def tonemap_device(self, n, d_rgb, d_rgba, stream=None):
         self._chk(lib().rrt_tonemap_device(self.h, n, d_rgb, d_rgba, stream))
+
+    def trace_rays(self, o, d, any_hit=False, mode="auto"):
+        """BVHAccel::intersect (bvh.cpp:103-113) of the rays (o [n, 3], d [n, 3]) under the context's
+        spacetime: a structured array [n] with the layout of rrt_hit (HIT_DTYPE).  any_hit: the
+        shadow query (status and steps only).  mode: "auto", "lane" or "wave" (RRT_TRACE_*)."""
+        o = np.asarray(o, np.float64).reshape(-1, 3)
+        d = np.asarray(d, np.float64).reshape(-1, 3)
+        if len(o) != len(d):
+            raise ValueError("o and d differ in length")
+        rays = np.empty(len(o), RAY_DTYPE)
+        rays["o"], rays["d"] = o, d
+        hits = np.zeros(len(o), HIT_DTYPE)
+        self._chk(lib().rrt_trace_rays(self.h, C.byref(trace_params(any_hit, mode)), _p(rays), len(rays), _p(hits)))
+        return hits
+
+    def trace_camera(self, frame_w, frame_h, x0, y0, w, h, any_hit=False, mode="auto"):
+        """The same query for the pixel-centre camera rays of a region of a frame_w x frame_h frame
+        (raytrace_pixel's ray with ns_aa == 1): a structured array [h, w], y = 0 at the bottom."""
+        hits = np.zeros((h, w), HIT_DTYPE)
+        self._chk(lib().rrt_trace_camera(self.h, C.byref(trace_params(any_hit, mode)), frame_w, frame_h, x0, y0, w, h,
+                                         _p(hits)))
+        return hits
+
+    def trace_rays_device(self, d_rays, n, d_hits, any_hit=False, mode="auto", stream=None):
+        """Asynchronous form on device buffers (rrt_ray [n] -> rrt_hit [n], 16-byte aligned), like
+        render_tiles_device."""
+        self._chk(lib().rrt_trace_rays_device(self.h, C.byref(trace_params(any_hit, mode)), d_rays, n, d_hits, stream))
+
+    def trace_camera_device(self, frame_w, frame_h, x0, y0, w, h, d_hits, any_hit=False, mode="auto", stream=None):
+        self._chk(lib().rrt_trace_camera_device(self.h, C.byref(trace_params(any_hit, mode)), frame_w, frame_h, x0, y0,
+                                                w, h, d_hits, stream))
 
     def stats(self):
         s = Stats()
