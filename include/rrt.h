@@ -117,7 +117,7 @@ enum { RRT_METRIC_SCHWARZSCHILD = 0, RRT_METRIC_KERR = 1 };
 typedef struct {
   uint32_t kind;              /* RRT_METRIC_SCHWARZSCHILD (r_s = 0: the reference's flat limit)
                                  or RRT_METRIC_KERR (build-defined, no reference) */
-  uint32_t reserved;
+  uint32_t flags;             /* RRT_SPACETIME_*; unknown bits are ignored (the field was `reserved`) */
   double center[3];           /* global_black_hole.o   (blackhole.cpp:5 default (0,1,0)) */
   double r_s;                 /* global_black_hole.r   (default 0.1); Kerr: 2M */
   double delta_theta;         /* global_black_hole.delta_theta (default 0.1); Kerr: the step's
@@ -126,6 +126,25 @@ typedef struct {
   double spin;                /* dimensionless a/M in [0, 1) */
   double axis[3];             /* spin axis (world; normalised by the library; 0 = scene up (0,1,0)) */
 } rrt_spacetime_desc;
+/* Lensed sky.  The reference bends every ray around the hole but looks the
+ * environment map up along the unbent ray (part1_code.cpp:107), and lets a captured ray see the sky
+ * too.  With this flag every query of the integrator -- camera, bounce and shadow rays -- runs the
+ * exit-mode march of RRT_TRACE_EXIT below, and
+ *   - a camera ray that ESCAPED takes the map along its exit direction (black without a map); one
+ *     that is CAPTURED or a MISS is black: the hole casts a shadow;
+ *   - the environment light's importance sample counts only if its shadow ray ESCAPED, with the
+ *     radiance of the map along that ray's exit direction; wi, the pdf, the BSDF term and every
+ *     RNG draw stay the reference's (the estimator stays unbiased: the integrand changes, the
+ *     sampling density does not);
+ *   - every other light keeps the reference's rule (a captured shadow ray counts as unoccluded).
+ * Rendered by two builds of the general per-pixel-loop kernel (any depth, every ray marched
+ * exactly, no proofs).  RRT_E_INVALID with RRT_RENDER_WAVEFRONT, RRT_RENDER_DEEP_SAMPLE,
+ * RRT_RENDER_COUNTERS or any of the reference's switch flags.  A property of the spacetime, which
+ * the members of a group share.  Clear: every output is the reference's. */
+enum { RRT_SPACETIME_LENSED_SKY = 1u << 0 };
+/* The far march of a Kerr photon ends at the first step that ends farther than this many M from
+ * the hole: the bending left beyond it is below M / r = 1e-3 rad. */
+#define RRT_SKY_FAR_M 1000.0
 /* Replaces: the `-B x y z r dtheta` override of the global black hole (main.cpp:139-145).
  * RRT_METRIC_KERR swaps BlackHole::next_micro_ray for an RK4 null-geodesic step in Kerr-Schild
  * coordinates; the rest of BVHAccel::intersect (segment tests, capture = no hit) is unchanged. */
@@ -328,8 +347,10 @@ typedef struct { double o[3], d[3]; } rrt_ray;   /* 48 bytes; d is used as given
 enum { RRT_RAY_MISS = 0,      /* the march ended with neither: the Schwarzschild step count is
                                  exhausted, or a Kerr escape or budget end */
        RRT_RAY_HIT = 1,
-       RRT_RAY_CAPTURED = 2 };/* the capture test (bvh.cpp:107; Kerr: the horizon test) fired
+       RRT_RAY_CAPTURED = 2,  /* the capture test (bvh.cpp:107; Kerr: the horizon test) fired
                                  before any hit */
+       RRT_RAY_ESCAPED = 3 }; /* RRT_TRACE_EXIT only: the ray left the scene for good; w_out is minus
+                                 its exit direction, every other hit field 0 / -1 */
 typedef struct {              /* 96 bytes; without a closest hit every field but status and steps
                                  is 0, prim and bsdf -1 */
   double hit_p[3];            /* Intersection::hit_p */
@@ -342,9 +363,23 @@ typedef struct {              /* 96 bytes; without a closest hit every field but
   uint32_t steps;             /* micro steps taken: index of the hit / capturing segment + 1; on
                                  a miss, all that were marched */
 } rrt_hit;
-enum { RRT_TRACE_ANY_HIT = 1u << 0 };  /* shadow query: status and steps are the closest-hit
+enum { RRT_TRACE_ANY_HIT = 1u << 0,    /* shadow query: status and steps are the closest-hit
                                           query's (both return at the first segment with a hit),
                                           the hit fields stay 0 / -1 */
+       RRT_TRACE_EXIT = 1u << 2 };     /* exit mode, below (bit 1 is unassigned and rejected) */
+/* RRT_TRACE_EXIT: where does an escaping ray end up?
+ * Schwarzschild: the stepper's updated u reaches <= 0 (or NaN) at the escape row j*; from there on
+ * the reference's rows jump through the hole and their hits and captures are ghosts.  The march
+ * stops at j* -- its capture test and walk, and all later rows, are not run -- and the record is
+ * RRT_RAY_ESCAPED with steps = j* + 1 and w_out = -e, e = (-u' x + u y) / |(u, u')| from that row's
+ * state before the update (RRT_RAY_MISS with steps = j* + 1 if u, u' are not finite or u' >= 0).
+ * A hit or capture on an earlier row keeps its record; a march without an escape row keeps its MISS.
+ * Kerr: a march that ended outgoing beyond the scene goes on, without segment queries, until a step
+ * ends beyond RRT_SKY_FAR_M x M: RRT_RAY_ESCAPED, w_out = minus that step's unit chord, steps as
+ * without the flag; a far march that outruns its own budget of steps, or a march that ended on
+ * the sweep or step budget, stays RRT_RAY_MISS.  Combines with RRT_TRACE_ANY_HIT (status, steps and
+ * an ESCAPED record's w_out are the same) and with every mode the metric allows; the modes' records
+ * are identical. */
 enum { RRT_TRACE_AUTO = 0,          /* wave per ray when every ray can hold a resident wave of its
                                        own at once (Schwarzschild), else lane per ray */
        RRT_TRACE_LANE_PER_RAY = 1,  /* one lane marches one ray */
@@ -395,6 +430,10 @@ int rrt_get_stats(const rrt_ctx* ctx, rrt_stats* out);
  * 3 atan2(a, b), 4 sinf((float)a), 5 cosf((float)a) (float results widened to double), 6 exp(a),
  * 7 log(a), 8 erf(a), 9 atan(a), 10 tan(a). */
 int rrt_libm_eval(rrt_ctx* ctx, int fn, const double* a, const double* b, double* out, uint64_t n);
+/* The device's EnvironmentLight::sample_dir (environment_light.cpp:146-148: the map's radiance
+ * along a direction, normalised by the lookup) on n host directions: dirs [n][3] -> rgb [n][3].
+ * RRT_E_INVALID without an environment map, RRT_E_NO_DEVICE on a host-only context. */
+int rrt_env_eval(rrt_ctx* ctx, const double* dirs, uint64_t n, float* rgb);
 /* Run-time proof audit.  The renderer skips marches whose results its proofs
  * determine (camera-ray miss, shadow-ray occlusion, pixel and strip miss, Kerr occlusion); their
  * margins are validated by sweeps.  With the audit set, every counting launch that runs the proofs

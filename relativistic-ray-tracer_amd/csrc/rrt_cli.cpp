@@ -6,7 +6,8 @@
 //   -a N T  adaptive batch / tolerance -H  hemisphere direct lighting  -p X Y DX DY  render a cell
 //   -b R  lens radius  -d D  focal distance  -B X Y Z R DTHETA  black hole (centre, r_s, step)
 // plus --seed S (keyed RNG seed), --device D and --kerr A [AX AY AZ] (Kerr spin a/M about the
-// axis, default +y; build-defined).  The interactive viewer is out of scope: -f is
+// axis, default +y; build-defined) and --lensed-sky (escaping rays see the environment
+// map along their exit direction).  The interactive viewer is out of scope: -f is
 // required.  Exit codes follow main.cpp (usage -> 1).
 #include <cstdio>
 #include <cstdlib>
@@ -36,6 +37,7 @@ static void usage(const char* binary) {
   std::printf("  --seed <INT>     Keyed RNG seed (default 0)   --device <INT> HIP device\n");
   std::printf("  --devices <D0,D1,...>  Render on several GPUs (block-cyclic tiles, RCCL gather)\n");
   std::printf("  --kerr <A> [<AX> <AY> <AZ>]  Kerr black hole, spin a/M in [0,1) about axis (default 0 1 0)\n");
+  std::printf("  --lensed-sky     Look the environment map up along the bent ray; the hole's shadow is black\n");
   std::printf("  -h               Print this help message\n");
 }
 
@@ -52,7 +54,7 @@ int main(int argc, char** argv) {
   unsigned long long seed = 0;
   int device = 0;
   std::vector<int> devices;  // --devices: several GPUs (rrt_group)
-  bool to_file = false;
+  bool to_file = false, lensed_sky = false;
   auto need = [&](int i, int n) {
     if (i + n >= argc) { usage(argv[0]); std::exit(1); }
   };
@@ -95,6 +97,7 @@ int main(int argc, char** argv) {
       }
       device = devices[0];
     }
+    else if (a == "--lensed-sky") { lensed_sky = true; }
     else if (a == "--kerr") {
       need(i, 1);
       kerr_spin = std::atof(argv[++i]);
@@ -156,6 +159,7 @@ int main(int argc, char** argv) {
   pt.set_seed(seed);
   pt.set_black_hole(hole, hole[3], hole[4]);
   if (kerr_spin >= 0) pt.set_kerr(kerr_spin, kerr_axis);
+  if (lensed_sky) pt.set_lensed_sky(true);
   // Application::set_up_pathtracer (application.cpp:622-628)
   pt.set_camera(&camera);
   pt.set_scene(scene);

@@ -280,6 +280,12 @@ struct QRec {
   uint32_t steps;  // micro steps taken: index of the hit / capturing segment + 1; else all marched
   bool captured;   // the march ended in the capture test (bvh.cpp:107; Kerr: the horizon test)
 };
+// What an exit-mode march (query / kerr_march with EXIT) reports about a ray that left
+// the scene: escaped, and then e = its direction far from the hole (unit up to rounding).
+struct ExitRec {
+  v3 e;
+  bool escaped;
+};
 
 // BVHAccel::intersect_micro (bvh.cpp:115-138) for one micro segment.  ANY: shadow query, stop
 // at the first accepted primitive (only the boolean is used; result-identical).
@@ -727,6 +733,18 @@ __device__ __forceinline__ void next_micro_at(const DHole& h, v3 no, v3& o, v3& 
     next_micro_impl<false>(h, no, o, d, max_t, rel, rel2, ok, mo);
   }
 }
+// Exit direction of the Schwarzschild stepper.  The escape row is the first whose
+// updated u (mo.v) is not > 0: from there on 1 / u is negative and the "segment" jumps through the
+// hole.  Far out u'' = -u, so from that row's state before the update (u, u' in the orbital plane
+// x, y) the ray runs to the polar angle where u = 0: the asymptote e = (-u' x + u y) / |(u, u')|,
+// each component two products and a sum, IEEE / and sqrt.  Escaped iff u, u' finite and u' < 0.
+__device__ __forceinline__ void exit_dir(const MicroOut& mo, ExitRec& xr) {
+  const double u = mo.u, up = mo.up;
+  const double s = sqrt(u * u + up * up);
+  const double cx = (-up) / s, cy = u / s;
+  xr.e = V(cx * mo.x.x + cy * mo.y.x, cx * mo.x.y + cy * mo.y.y, cx * mo.x.z + cy * mo.y.z);
+  xr.escaped = isfinite(u) && isfinite(up) && up < 0.0;
+}
 __device__ __forceinline__ void next_micro(const DHole& h, v3& o, v3& d, double& max_t) {
   v3 rel;
   double rel2;
@@ -817,8 +835,15 @@ constexpr int V_KERR = 3;
 constexpr int V_SW = 4;
 enum { SW_THIN_LENS = 1u, SW_NO_ADAPTIVE = 2u, SW_ENV_HEMI = 4u, SW_MF_HEMI = 8u };
 __device__ __forceinline__ uint32_t sw_illum(const KParams& kp) { return ((kp.sw >> 4) & 3u) ^ 2u; }  // ILLUM
+// V_SKY / V_KERR_SKY: the general builds with the lensed sky (RRT_SPACETIME_LENSED_SKY):
+// every query runs the exit-mode march and an escaping ray looks the environment map up along its
+// exit direction.  Per-pixel-loop kernel only (rrt_kernel.hip); no proofs.
+constexpr int V_SKY = 5;
+constexpr int V_KERR_SKY = 6;
 __host__ __device__ constexpr bool is_lean(int v) { return v == 1 || v == 2; }
-__host__ __device__ constexpr int general_of(int v) { return v == V_KERR || v == V_SW ? v : 0; }  // non-LEAN build
+__host__ __device__ constexpr bool is_sky(int v) { return v == V_SKY || v == V_KERR_SKY; }
+__host__ __device__ constexpr bool is_kerr_build(int v) { return v == V_KERR || v == V_KERR_SKY; }
+__host__ __device__ constexpr int general_of(int v) { return v == V_KERR || v == V_SW || is_sky(v) ? v : 0; }  // non-LEAN build
 
 // ------------------------------------------------------------------ Kerr (build-defined)
 // The reference has no Kerr metric; this integrator is this build's design
@@ -931,15 +956,16 @@ __device__ __forceinline__ void kerr_init(const DHole& h, v3 o, v3 d, v3& q, v3&
 // true); h = delta_theta * r / |dq/dl| (the path advances delta_theta * r); the polar angle
 // swept; then the classical RK4 update.
 // st: step stretch (1: the march; the occlusion proof's coarse march takes kp.kproof.stretch)
-template <class A>
+// FAR: a step of the far march (kerr_far_march): no escape test, no swept angle; q, p as the march's
+template <bool FAR = false, class A>
 __device__ __forceinline__ bool kerr_advance(const DHole& h, v3& q, v3& p, double& swept, A& ar, double st = 1.0) {
   v3 dq1, dp1;
   double r, rr;
   kerr_rhs(h, q, p, dq1, dp1, r, ar);
   const double rho2 = norm2(q);
-  if (rho2 > h.r_esc2 && dot(q, dq1) > 0.0) return true;  // outgoing beyond the scene
+  if (!FAR && rho2 > h.r_esc2 && dot(q, dq1) > 0.0) return true;  // outgoing beyond the scene
   const double hh = ar.dv((h.dt * r) * st, ar.sq(norm2(dq1)));  // (dt r) * 1 = dt r exactly
-  swept += ar.dv(hh * ar.sq(norm2(cross(q, dq1))), rho2);  // polar angle of this step
+  if (!FAR) swept += ar.dv(hh * ar.sq(norm2(cross(q, dq1))), rho2);  // polar angle of this step
   const double half = 0.5 * hh;
   // stages 2-4 folded into running sums as they come: ((k1 + 2 k2) + 2 k3) + k4, the same
   // operations in the same order as summing at the end, with one stage live at a time
@@ -979,8 +1005,9 @@ __device__ __forceinline__ void audit_note(const KParams& kp, int k, bool violat
   if (violated) atomicAdd(kp.audit + 2 * k + 1, 1ull);
 }
 __device__ __forceinline__ bool kerr_occluded_proof(const KParams& kp, v3 o, v3 d);
-template <bool ANY, bool COUNT>
-__device__ __forceinline__ bool kerr_march(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn, QRec* qr = nullptr);
+template <bool ANY, bool COUNT, bool EXIT = false>
+__device__ __forceinline__ bool kerr_march(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn, QRec* qr = nullptr,
+                                           ExitRec* xr = nullptr);
 template <bool ANY, bool COUNT>
 __device__ __forceinline__ bool query_kerr(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn) {
   // shadow rays: the occlusion proof first (never in the reference-work counts)
@@ -993,9 +1020,37 @@ __device__ __forceinline__ bool query_kerr(const KParams& kp, v3 o, v3 d, Isect*
   }
   return kerr_march<ANY, COUNT>(kp, o, d, is, cn);
 }
-// the march of query_kerr (no proof)
-template <bool ANY, bool COUNT>
-__device__ __forceinline__ bool kerr_march(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn, QRec* qr) {
+// The far march: a photon that left the march outgoing beyond r_esc, at (q, p) with a
+// the last segment's end (first: no step was taken yet, a is the ray's origin), goes on with the
+// march's own steps -- no segment queries, nothing is out there -- until a step ends beyond
+// RRT_SKY_FAR_M x M of the hole: that step's unit chord, built as the march builds a segment's
+// direction, is the exit direction.  A fresh budget of kerr_max_steps; running out of it: not escaped.
+__device__ __forceinline__ void kerr_far_march(const DHole& h, v3 q, v3 p, v3 a, ExitRec& xr) {
+  const double far = RRT_SKY_FAR_M * h.m, far2 = far * far;
+#pragma unroll 1
+  for (int j = 0; j < h.kerr_max_steps; ++j) {
+    v3 q1 = q, p1 = p;
+    double sw = 0.0;
+    KArith<true> fast;
+    kerr_advance<true>(h, q1, p1, sw, fast);
+    if (__builtin_expect(!fast.ok, 0)) {
+      KArith<false> ieee;
+      q1 = q; p1 = p;
+      kerr_advance<true>(h, q1, p1, sw, ieee);
+    }
+    if (norm2(q1) > far2) {
+      const v3 seg = kerr_world(h, q1) - (j == 0 ? a : kerr_world(h, q));
+      const double inv = xdiv(1., norm(seg));
+      xr.e = V(seg.x * inv, seg.y * inv, seg.z * inv);
+      xr.escaped = true;
+      return;
+    }
+    q = q1; p = p1;
+  }
+}
+// the march of query_kerr (no proof).  EXIT: an escaping photon goes on to its exit direction (*xr)
+template <bool ANY, bool COUNT, bool EXIT>
+__device__ __forceinline__ bool kerr_march(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn, QRec* qr, ExitRec* xr) {
   const DHole& h = kp.hole;
   v3 q, p;
   kerr_init(h, o, d, q, p);
@@ -1014,7 +1069,10 @@ __device__ __forceinline__ bool kerr_march(const KParams& kp, v3 o, v3 d, Isect*
       escaped = kerr_advance(h, q1, p1, sw1, ieee);
     }
     if (qr) qr->steps = (uint32_t)j + 1u;  // the step being taken: the one that escapes, captures or hits
-    if (escaped) return false;
+    if (escaped) {
+      if (EXIT && xr) kerr_far_march(h, q, p, a, *xr);
+      return false;
+    }
     q = q1; p = p1; swept = sw1;
     if (COUNT) cn.micro++;
     if (kerr_r2(h, q) <= rh2) {  // captured
@@ -1270,9 +1328,13 @@ __device__ __forceinline__ bool shadow_occluded_proof(const KParams& kp, v3 o, v
 // W4: walks may take the 4-wide search tree -- the LEAN builds' choice; the general and Kerr builds
 // walk the binary tree (with the 4-wide walk inlined their scratch grew 2.5-3x: general batch kernel
 // 592 -> 1488 B/lane, Kerr 720 -> 2304 and cfg5 1.41 -> 3.76 s per frame, profiles/r05_ab_kerr_bvh4.txt)
-template <bool ANY, bool COUNT, bool KERR = false, bool W4 = true>
+// EXIT: the exit-mode march (no proofs): the Schwarzschild march stops at the escape
+// row -- that row's capture test and walk, and every later row, are not run -- and *xr (if given)
+// says whether and where the ray escaped; Kerr: kerr_march's far march.
+template <bool ANY, bool COUNT, bool KERR = false, bool W4 = true, bool EXIT = false>
 RRT_QUERY_ATTR bool query(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn, bool any_rt = false,
-                          QRec* qr = nullptr) {
+                          QRec* qr = nullptr, ExitRec* xr = nullptr) {
+  if (KERR && EXIT) return kerr_march<ANY, COUNT, true>(kp, o, d, is, cn, qr, xr);
   if (KERR) return qr ? kerr_march<ANY, COUNT>(kp, o, d, is, cn, qr) : query_kerr<ANY, COUNT>(kp, o, d, is, cn);
   if (qr) qr->steps = (uint32_t)kp.hole.steps;  // all marched, unless a segment below ends the march
   if (COUNT && !kp.count_exec && !(kp.diag & 2)) cn.query++;
@@ -1283,9 +1345,16 @@ RRT_QUERY_ATTR bool query(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn
     RRT_T0(tm0);
     v3 rel;
     double rel2;
-    next_micro_at(kp.hole, e, o, d, max_t, rel, rel2);
+    MicroOut mo;
+    next_micro_at(kp.hole, e, o, d, max_t, rel, rel2, EXIT ? &mo : nullptr);
     RRT_ACC(t_micro, tm0);
     if (COUNT) cn.micro++;
+    if (EXIT && !(mo.v > 0.0)) {  // the escape row (NaN counts)
+      RRT_QACC(tq0);
+      if (qr) qr->steps = (uint32_t)j + 1u;
+      if (xr) exit_dir(mo, *xr);
+      return false;
+    }
     if (sphere_t_rel(rel, rel2, kp.hole.r2, d, max_t)) {  // captured
       RRT_QACC(tq0);
       if (qr) { qr->steps = (uint32_t)j + 1u; qr->captured = true; }

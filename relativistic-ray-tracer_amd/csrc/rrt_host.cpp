@@ -35,7 +35,8 @@ hipError_t rrt_launch_first(const KParams& kp, const KParams* d_kp, int lean, in
 hipError_t rrt_launch_pixel_proof(const KParams* d_kp, uint32_t n_pixels, bool strips, hipStream_t stream);
 hipError_t rrt_launch_heavy(const KParams* d_kp, int lean, int waves, int nw, uint32_t grid, int drain, hipStream_t stream);
 hipError_t rrt_launch_path(const KParams* d_kp, int waves, uint32_t grid, hipStream_t stream);
-hipError_t rrt_launch_trace(const KParams* d_kp, const TraceArgs& a, int kerr, int any, int mode, int n_cu, int* mode_out,
+hipError_t rrt_launch_env(const DEnv& env, uint64_t n, const double* dirs, float* rgb, hipStream_t stream);
+hipError_t rrt_launch_trace(const KParams* d_kp, const TraceArgs& a, int kerr, int any, int exit, int mode, int n_cu, int* mode_out,
                             hipStream_t stream);
 hipError_t rrt_launch_unpack(const uint32_t* tiles, uint32_t n_tiles, uint32_t ts, uint32_t fw, uint32_t fh,
                              const float* rgb_p, const int32_t* cnt_p, float* rgb, int32_t* cnt, hipStream_t stream);
@@ -168,6 +169,7 @@ struct rrt_ctx {
   DCamera cam{};
   double lens_r = 0.0, focal = 0.0;  // Camera::lensRadius / focalDistance (thin lens, RRT_RENDER_THIN_LENS)
   DHole hole{};
+  bool lensed_sky = false;  // RRT_SPACETIME_LENSED_SKY
   // device scene
   DNode* d_nodes = nullptr;
   DPrimGeo* d_geo = nullptr;
@@ -1258,6 +1260,7 @@ extern "C" int rrt_set_spacetime(rrt_ctx* c, const rrt_spacetime_desc* st) {
     h.r_hor = h.m + std::sqrt(h.m * h.m - h.a2);
   }
   c->hole = h;
+  c->lensed_sky = (st->flags & RRT_SPACETIME_LENSED_SKY) != 0;
   return RRT_OK;
 }
 
@@ -1568,6 +1571,14 @@ static int launch(rrt_ctx* c, const rrt_render_params* p, const uint32_t* tiles,
                                   "(Ray::depth is size_t and wraps below 0; only Russian roulette ends it), beyond "
                                   "RRT_MAX_DEPTH");
   if (sw) { kp.miss.on = 0u; kp.occ.on = 0u; }
+  // the lensed sky (RRT_SPACETIME_LENSED_SKY): the general per-pixel-loop builds V_SKY /
+  // V_KERR_SKY (rrt_kernel.hip), every query the exit-mode march, no proof
+  const bool sky = c->lensed_sky;
+  if (sky && (sw || (p->flags & (RRT_RENDER_WAVEFRONT | RRT_RENDER_DEEP_SAMPLE | RRT_RENDER_COUNTERS))))
+    return fail(c, RRT_E_INVALID, "the lensed sky (RRT_SPACETIME_LENSED_SKY) renders in the per-pixel-loop kernel only: "
+                                  "not with RRT_RENDER_WAVEFRONT, RRT_RENDER_DEEP_SAMPLE, RRT_RENDER_COUNTERS or the "
+                                  "reference's switch flags");
+  if (sky) { kp.miss.on = 0u; kp.occ.on = 0u; kp.kproof.on = 0u; }
   // bounce paths (depth >= 2): the per-pixel-loop kernel by default; RRT_RENDER_DEEP_SAMPLE selects
   // the per-sample refill kernel (rrt_sample.hip, one lane per pixel, a lane whose pixel is done
   // takes the next at the next sample boundary) -- m3 A/B, profiles/r03_ab_deep.jsonl: 177 ms
@@ -1586,8 +1597,9 @@ static int launch(rrt_ctx* c, const rrt_render_params* p, const uint32_t* tiles,
                      (uint64_t)all_lights(c).size() * std::max<uint32_t>(1u, p->ns_area_light) < 2048u))
     return fail(c, RRT_E_INVALID, "RRT_RENDER_WAVEFRONT (the path pool kernel) renders max_ray_depth >= 2 "
                                   "Schwarzschild frames without counters or switches, n_lights x ns_area_light < 2048");
-  const bool pixel_loop = !path_pool && ((deep && !deep_sample) || (p->flags & RRT_RENDER_PIXEL_LOOP) || sw);
-  const int lean = kerr ? 3 /* V_KERR */
+  const bool pixel_loop = !path_pool && ((deep && !deep_sample) || (p->flags & RRT_RENDER_PIXEL_LOOP) || sw || sky);
+  const int lean = sky ? (kerr ? 6 /* V_KERR_SKY */ : 5 /* V_SKY */)
+                 : kerr ? 3 /* V_KERR */
                  : sw ? 4 /* V_SW */
                  : (!deep && !count && !c->env_w && !p->direct_hemisphere) ? c->lean : 0;
   const uint32_t wv = p->variant & 0xffu;
@@ -1963,7 +1975,7 @@ static int launch(rrt_ctx* c, const rrt_render_params* p, const uint32_t* tiles,
     HIPCHK(c, rrt_launch_path(c->d_kp, waves, grid, stream));
   } else if (pixel_loop) {
     std::snprintf(name, sizeof(name), "%srrt_render_kernel<%s, %s, %d, ...>", deep_list ? "rrt_pixel_proof_kernel + " : "",
-                  tf[deep || sw], tf[count], lean == 2 ? 0 : lean);
+                  tf[deep || sw || sky], tf[count], lean == 2 ? 0 : lean);
     if (deep_list) HIPCHK(c, rrt_launch_pixel_proof(c->d_kp, kp.n_pixels, kp.strip_list != nullptr, stream));
     HIPCHK(c, hipEventRecord(c->ev_main[ring], stream));
     HIPCHK(c, rrt_launch_render(kp, c->d_kp, deep, count, lean, waves, grid, stream));
@@ -2070,6 +2082,29 @@ extern "C" int rrt_libm_eval(rrt_ctx* c, int fn, const double* a, const double* 
   return RRT_OK;
 }
 
+extern "C" int rrt_env_eval(rrt_ctx* c, const double* dirs, uint64_t n, float* rgb) {
+  if (!c || (n && (!dirs || !rgb))) return fail(c, RRT_E_INVALID, "bad argument");
+  if (!c->env_w) return fail(c, RRT_E_INVALID, "no environment map (rrt_set_envmap)");
+  if (c->device < 0) return fail(c, RRT_E_NO_DEVICE, "no device");
+  if (n == 0) return RRT_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  double* dd = nullptr;
+  float* dr = nullptr;
+  struct Free {
+    void** p[2];
+    ~Free() { for (void** q : p) if (*q) (void)hipFree(*q); }
+  } guard{{(void**)&dd, (void**)&dr}};
+  HIPCHK(c, hipMalloc(&dd, sizeof(double) * 3 * n));
+  HIPCHK(c, hipMalloc(&dr, sizeof(float) * 3 * n));
+  HIPCHK(c, hipMemcpy(dd, dirs, sizeof(double) * 3 * n, hipMemcpyHostToDevice));
+  DEnv env{};
+  env.tex = c->d_env_tex; env.pdf = c->d_env_pdf; env.conds = c->d_env_conds; env.marg = c->d_env_marg;
+  env.w = c->env_w; env.h = c->env_h;
+  HIPCHK(c, rrt_launch_env(env, n, dd, dr, (hipStream_t)0));
+  HIPCHK(c, hipMemcpy(rgb, dr, sizeof(float) * 3 * n, hipMemcpyDeviceToHost));
+  return RRT_OK;
+}
+
 // ---------------------------------------------------------------- ray queries (rrt_query.hip)
 // One launch of the ray-query kernels: n caller rays (d_rays) or, with cam, the pixel-centre
 // camera rays of the region (x0, y0, w, n / w) of a fw x fh frame.  The context's workspace holds the
@@ -2078,7 +2113,7 @@ static int trace_launch(rrt_ctx* c, const rrt_trace_params* tp, bool cam, const 
                         uint32_t x0, uint32_t y0, uint32_t w, uint32_t n, rrt_hit* d_hits, hipStream_t stream) {
   static_assert(sizeof(rrt_ray) == 48 && sizeof(rrt_hit) == 96, "rrt_ray / rrt_hit layout (rrt_query.hip stores)");
   const uint32_t flags = tp ? tp->flags : 0u, mode = tp ? tp->mode : (uint32_t)RRT_TRACE_AUTO;
-  if (flags & ~(uint32_t)RRT_TRACE_ANY_HIT) return fail(c, RRT_E_INVALID, "unknown rrt_trace_params flags");
+  if (flags & ~(uint32_t)(RRT_TRACE_ANY_HIT | RRT_TRACE_EXIT)) return fail(c, RRT_E_INVALID, "unknown rrt_trace_params flags");
   if (mode > RRT_TRACE_WAVE_PER_RAY) return fail(c, RRT_E_INVALID, "unknown rrt_trace_params mode");
   if (!c->has_scene) return fail(c, RRT_E_INVALID, "no scene (rrt_set_scene)");
   if (cam && !c->has_camera) return fail(c, RRT_E_INVALID, "no camera (rrt_set_camera)");
@@ -2105,7 +2140,7 @@ static int trace_launch(rrt_ctx* c, const rrt_trace_params* tp, bool cam, const 
   a.hits = d_hits;
   a.slot_prim = c->d_leaf;
   a.n = n; a.x0 = x0; a.y0 = y0; a.w = w ? w : 1u;
-  HIPCHK(c, rrt_launch_trace(c->d_kp, a, kerr ? 1 : 0, (flags & RRT_TRACE_ANY_HIT) ? 1 : 0, (int)mode, c->n_cu, nullptr,
+  HIPCHK(c, rrt_launch_trace(c->d_kp, a, kerr ? 1 : 0, (flags & RRT_TRACE_ANY_HIT) ? 1 : 0, (flags & RRT_TRACE_EXIT) ? 1 : 0, (int)mode, c->n_cu, nullptr,
                              stream));
   return RRT_OK;
 }

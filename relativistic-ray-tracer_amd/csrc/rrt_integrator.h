@@ -9,9 +9,11 @@ namespace rrt {
 
 // ------------------------------------------------------------------ integrator (part1_code.cpp)
 // `trace` = the geodesic-marched BVH query; DEEP (bounce) builds and depth <= 1 builds share it.
+// The lensed-sky builds (V_SKY, V_KERR_SKY) run the exit-mode march for every query; xr: where the
+// ray went if it hit nothing (they only).
 template <bool ANY, bool COUNT, bool DEEP, int LEAN>
-__device__ __forceinline__ bool trace(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn) {
-  return query<ANY, COUNT, LEAN == V_KERR, is_lean(LEAN)>(kp, o, d, is, cn);
+__device__ __forceinline__ bool trace(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn, ExitRec* xr = nullptr) {
+  return query<ANY, COUNT, is_kerr_build(LEAN), is_lean(LEAN), is_sky(LEAN)>(kp, o, d, is, cn, false, nullptr, xr);
 }
 
 // LEAN: area/point lights only, no microfacet BSDF.  The shading frame is rebuilt per light sample
@@ -33,6 +35,15 @@ __device__ spec direct_importance(const KParams& kp, Rng& g, const Isect& is, Co
       const Frame f = coord_space(is.n);
       v3 w_in = to_local(f, wi_world);
       if (w_in.z < 0) continue;
+      if (is_sky(LEAN) && l.type == 5u) {
+        // lensed sky: the environment light's sample counts iff its shadow ray escapes, with the
+        // map's radiance along the exit direction; wi, pdf, the BSDF term and the draws as they are
+        ExitRec xr = {V(0.0, 0.0, 0.0), false};
+        if (trace<true, COUNT, DEEP, LEAN>(kp, is.hit_p + smul(EPS_D, wi_world), wi_world, nullptr, cn, &xr) || !xr.escaped)
+          continue;
+        L = L + ((env_dir(kp.env, xr.e) * bsdf_f<LEAN>(b, to_local(f, is.w_out), w_in)) * (float)w_in.z) / pdf;
+        continue;
+      }
       spec contrib = ((sample * bsdf_f<LEAN>(b, to_local(f, is.w_out), w_in)) * (float)w_in.z) / pdf;
       if (!trace<true, COUNT, DEEP, LEAN>(kp, is.hit_p + smul(EPS_D, wi_world), wi_world, nullptr, cn)) L = L + contrib;
     }

@@ -17,8 +17,12 @@ namespace rrt {
 template <bool DEEP, bool COUNT, int LEAN, int W = 0, class LV = LevelsPriv>
 __device__ __forceinline__ spec est_radiance(const KParams& kp, Rng& g, v3 o, v3 d, Counters& cn, LV lv = LV()) {  // :103-123
   Isect is;
-  if (camera_proven_miss<COUNT, LEAN == V_KERR, LEAN == 0, W>(kp, o, d, cn) ||
-      !trace<false, COUNT, DEEP, LEAN>(kp, o, d, &is, cn))  // miss: envLight->sample_dir(r), unbent r
+  if (is_sky(LEAN)) {  // lensed sky: the map along an escaping ray's exit direction; the hole's shadow is black
+    ExitRec xr = {V(0.0, 0.0, 0.0), false};
+    if (!trace<false, COUNT, DEEP, LEAN>(kp, o, d, &is, cn, &xr))
+      return (xr.escaped && kp.env.w) ? env_dir(kp.env, xr.e) : S(0, 0, 0);
+  } else if (camera_proven_miss<COUNT, LEAN == V_KERR, LEAN == 0, W>(kp, o, d, cn) ||
+             !trace<false, COUNT, DEEP, LEAN>(kp, o, d, &is, cn))  // miss: envLight->sample_dir(r), unbent r
     return (!is_lean(LEAN) && kp.env.w) ? env_dir(kp.env, d) : S(0, 0, 0);
   if (LEAN == V_SW && sw_illum(kp) != 2u) {  // ILLUM 0 / 1 / 3 (:108-122)
     const uint32_t il = sw_illum(kp);
@@ -197,6 +201,14 @@ __global__ void rrt_libm_kernel(int fn, uint64_t n, const double* a, const doubl
     out[k] = r;
   }
 }
+// EnvironmentLight::sample_dir as the kernels evaluate it (rrt_device.h env_dir) on n directions:
+// rrt_env_eval, the checker's handle on the lensed sky's lookups (tests/test_gpu_lensed_sky.py)
+__global__ void rrt_env_kernel(const DEnv env, uint64_t n, const double* dirs, float* rgb) {
+  for (uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; k < n; k += (uint64_t)gridDim.x * blockDim.x) {
+    const rrt::spec s = rrt::env_dir(env, rrt::V(dirs[3 * k], dirs[3 * k + 1], dirs[3 * k + 2]));
+    rgb[3 * k] = s.r; rgb[3 * k + 1] = s.g; rgb[3 * k + 2] = s.b;
+  }
+}
 
 // ------------------------------------------------------------------ launch shims (C++ linkage)
 // Kernel selection: deep / counting variants are built once (1 wave per SIMD budget); the
@@ -208,7 +220,12 @@ hipError_t rrt_launch_render(const KParams& kp, const KParams* d_kp, int deep, i
   // the bounce levels in LDS (frames of max_ray_depth <= 4; RRT_AB_NO_LEVEL_LDS=1 keeps them private, A/B)
   static const bool no_lv = [] { const char* e = std::getenv("RRT_AB_NO_LEVEL_LDS"); return e && e[0] == '1'; }();
   const bool lv4 = deep && !count && kp.max_ray_depth <= 4u && !no_lv;
-  if (lean == rrt::V_SW) {  // the reference's switches as run-time flags: one bounce-capable build
+  if (lean == rrt::V_SKY) {  // the lensed sky: one bounce-capable build per metric, no counters; 2 waves/SIMD
+                             // (cfg3's framing 141.8 -> 117.4 ms against 1; the cfg5 crop the same, profiles/README.md)
+    RRT_LAUNCH(true, false, rrt::V_SKY, 2);
+  } else if (lean == rrt::V_KERR_SKY) {
+    RRT_LAUNCH(true, false, rrt::V_KERR_SKY, 2);
+  } else if (lean == rrt::V_SW) {  // the reference's switches as run-time flags: one bounce-capable build
     if (count) RRT_LAUNCH(true, true, rrt::V_SW, 1); else RRT_LAUNCH(true, false, rrt::V_SW, 1);
   } else if (lean == rrt::V_KERR) {  // the Kerr builds (general integrator)
     if (deep) {
@@ -264,6 +281,13 @@ hipError_t rrt_launch_libm(int fn, uint64_t n, const double* a, const double* b,
   if (grid > 8192) grid = 8192;
   if (grid == 0) grid = 1;
   hipLaunchKernelGGL(rrt_libm_kernel, dim3((uint32_t)grid), dim3(256), 0, stream, fn, n, a, b, out);
+  return hipGetLastError();
+}
+hipError_t rrt_launch_env(const DEnv& env, uint64_t n, const double* dirs, float* rgb, hipStream_t stream) {
+  uint64_t grid = (n + 255) / 256;
+  if (grid > 8192) grid = 8192;
+  if (grid == 0) grid = 1;
+  hipLaunchKernelGGL(rrt_env_kernel, dim3((uint32_t)grid), dim3(256), 0, stream, env, n, dirs, rgb);
   return hipGetLastError();
 }
 hipError_t rrt_launch_tonemap(uint32_t n, const float* rgb, uint32_t* out, float exposure, float inv_gamma,

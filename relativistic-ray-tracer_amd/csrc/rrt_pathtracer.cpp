@@ -153,6 +153,7 @@ void PathTracer::apply_spacetime() {
   rrt_spacetime_desc st;
   std::memset(&st, 0, sizeof(st));
   st.kind = kerr_spin_ < 0 ? RRT_METRIC_SCHWARZSCHILD : RRT_METRIC_KERR;
+  st.flags = lensed_sky_ ? RRT_SPACETIME_LENSED_SKY : 0u;
   for (int i = 0; i < 3; ++i) st.center[i] = hole_c_[i];
   st.r_s = hole_rs_; st.delta_theta = hole_dt_;
   st.spin = kerr_spin_ < 0 ? 0.0 : kerr_spin_;
@@ -218,6 +219,11 @@ void PathTracer::set_black_hole(const double center[3], double r_s, double delta
 void PathTracer::set_kerr(double spin, const double axis[3]) {
   kerr_spin_ = spin;
   if (axis) for (int i = 0; i < 3; ++i) kerr_axis_[i] = axis[i];
+  apply_spacetime();
+}
+
+void PathTracer::set_lensed_sky(bool on) {
+  lensed_sky_ = on;
   apply_spacetime();
 }
 

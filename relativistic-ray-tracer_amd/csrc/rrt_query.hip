@@ -125,15 +125,109 @@ __global__ __launch_bounds__(256) void rrt_trace_wave_kernel(const KParams* __re
   if (lane == 0) store_hit(a, i, RRT_RAY_MISS, (uint32_t)steps, false, is, qr);
 }
 
+// ------------------------------------------------------------------ exit mode (RRT_TRACE_EXIT)
+// Builds of their own, so the kernels above stay as they are.  DESIGN.md §11.
+namespace rrt {
+// the record of a march that ended at its escape row (or, Kerr, in the far march): ESCAPED with
+// w_out = -e, or MISS; every other hit field 0 / -1
+__device__ __forceinline__ void store_exit(const TraceArgs& a, uint32_t i, uint32_t steps, const ExitRec& xr) {
+  double2* h = reinterpret_cast<double2*>(a.hits) + 6 * (size_t)i;
+  const double2 z = make_double2(0.0, 0.0);
+  h[0] = z; h[1] = z; h[2] = z;
+  h[3] = xr.escaped ? make_double2(-xr.e.x, -xr.e.y) : z;
+  h[4] = xr.escaped ? make_double2(-xr.e.z, 0.0) : z;
+  uint4 tail;
+  tail.x = xr.escaped ? RRT_RAY_ESCAPED : RRT_RAY_MISS; tail.y = 0xffffffffu; tail.z = 0xffffffffu; tail.w = steps;
+  *reinterpret_cast<uint4*>(h + 5) = tail;
+}
+}  // namespace rrt
+
+// rrt_trace_lane_kernel with the exit-mode march
+template <bool KERR, bool ANY, bool CAM>
+__global__ __launch_bounds__(256) void rrt_trace_exit_lane_kernel(const KParams* __restrict__ kpp, const TraceArgs a) {
+  using namespace rrt;
+  const KParams& kp = *kpp;
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= a.n) return;
+  v3 o, d;
+  load_ray<CAM>(kp, a, i, o, d);
+  Isect is;
+  QRec qr = {-1, 0.0, 0u, false};
+  ExitRec xr = {V(0.0, 0.0, 0.0), false};
+  Counters cn = {};
+  const bool hit = query<ANY, false, KERR, !KERR, true>(kp, o, d, &is, cn, false, &qr, &xr);
+  if (hit || qr.captured) store_hit(a, i, hit ? RRT_RAY_HIT : RRT_RAY_CAPTURED, qr.steps, hit && !ANY, is, qr);
+  else store_exit(a, i, qr.steps, xr);
+}
+
+// rrt_trace_wave_kernel in exit mode: the escape row is a property of the chain alone, so it is
+// found while the chain is generated, wave-uniform; the chain stops there, and lanes at or beyond it
+// walk nothing
+template <bool ANY, bool CAM>
+__global__ __launch_bounds__(256) void rrt_trace_exit_wave_kernel(const KParams* __restrict__ kpp, const TraceArgs a) {
+  using namespace rrt;
+  const KParams& kp = *kpp;
+  const int lane = (int)(threadIdx.x & 63u);
+  const uint32_t i = blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (i >= a.n) return;  // the whole wave
+  v3 o, d;
+  load_ray<CAM>(kp, a, i, o, d);
+  double max_t = 0.0;
+  v3 e = o + vmul(d, max_t);
+  Isect is;
+  QRec qr = {-1, 0.0, 0u, false};
+  ExitRec xr = {V(0.0, 0.0, 0.0), false};
+  Counters cn = {};
+  const int steps = kp.hole.steps;
+  for (int base = 0; base < steps; base += 64) {
+    const int n_round = steps - base < 64 ? steps - base : 64;
+    v3 so = o, sd = d, se = e;
+    double smt = max_t;
+    int cap = -1, esc = -1;
+    for (int l = 0; l < n_round; ++l) {
+      v3 rel;
+      double rel2;
+      MicroOut mo;
+      next_micro_at(kp.hole, e, o, d, max_t, rel, rel2, &mo);
+      // wave-uniform by construction, as the capture flag below: scalar branches
+      if (__builtin_amdgcn_readfirstlane((int)!(mo.v > 0.0)) != 0) {
+        esc = l;
+        exit_dir(mo, xr);
+        break;
+      }
+      const bool c = __builtin_amdgcn_readfirstlane((int)sphere_t_rel(rel, rel2, kp.hole.r2, d, max_t)) != 0;
+      e = o + vmul(d, max_t);
+      if (lane == l) { so = o; sd = d; smt = max_t; se = e; }
+      if (c) { cap = l; break; }
+    }
+    const int n_seg = cap >= 0 ? cap : esc >= 0 ? esc : n_round;
+    bool hit = false;
+    if (lane < n_seg) hit = segment_query<ANY, false, true>(kp, so, sd, smt, se, &is, cn, false, &qr);
+    const bool captured = lane == cap;
+    const uint64_t flagged = __ballot(hit || captured);
+    if (flagged) {
+      if (lane == __ffsll((unsigned long long)flagged) - 1)
+        store_hit(a, i, captured ? RRT_RAY_CAPTURED : RRT_RAY_HIT, (uint32_t)(base + lane) + 1u, hit && !ANY, is, qr);
+      return;
+    }
+    if (esc >= 0) {  // no hit before the escape row
+      if (lane == 0) store_exit(a, i, (uint32_t)(base + esc) + 1u, xr);
+      return;
+    }
+  }
+  if (lane == 0) store_hit(a, i, RRT_RAY_MISS, (uint32_t)steps, false, is, qr);
+}
+
 // ------------------------------------------------------------------ launch shim (C++ linkage)
 // mode: RRT_TRACE_*; AUTO takes wave-per-ray when every ray can hold a resident wave of its own at
 // once -- n <= CUs x the wave kernel's resident waves per CU -- since below that count lane-per-ray
 // could not fill the machine anyway (Schwarzschild only; DESIGN.md §5 has the measured crossing).
 // *mode_out: the mode launched.
-hipError_t rrt_launch_trace(const KParams* d_kp, const TraceArgs& a, int kerr, int any, int mode, int n_cu, int* mode_out,
-                            hipStream_t stream) {
+hipError_t rrt_launch_trace(const KParams* d_kp, const TraceArgs& a, int kerr, int any, int exit, int mode, int n_cu,
+                            int* mode_out, hipStream_t stream) {
   const bool cam = a.rays == nullptr;
 #define RRT_WAVE_K(A, C) rrt_trace_wave_kernel<A, C>
+#define RRT_WAVE_X(A, C) rrt_trace_exit_wave_kernel<A, C>
 #define RRT_PICK(F, ...)                                          \
   do {                                                            \
     if (any) { if (cam) F(true, true, ##__VA_ARGS__); else F(true, false, ##__VA_ARGS__); } \
@@ -145,8 +239,10 @@ hipError_t rrt_launch_trace(const KParams* d_kp, const TraceArgs& a, int kerr, i
       int blocks = 0;
       hipError_t e = hipSuccess;
 #define RRT_OCC(A, C) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, RRT_WAVE_K(A, C), 256, 0)
-      RRT_PICK(RRT_OCC);
+#define RRT_OCC_X(A, C) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, RRT_WAVE_X(A, C), 256, 0)
+      if (exit) RRT_PICK(RRT_OCC_X); else RRT_PICK(RRT_OCC);
 #undef RRT_OCC
+#undef RRT_OCC_X
       if (e != hipSuccess) return e;
       if ((uint64_t)a.n <= (uint64_t)n_cu * 4u * (uint64_t)blocks) mode = RRT_TRACE_WAVE_PER_RAY;
     }
@@ -155,15 +251,21 @@ hipError_t rrt_launch_trace(const KParams* d_kp, const TraceArgs& a, int kerr, i
   if (mode == RRT_TRACE_WAVE_PER_RAY) {
     const uint32_t grid = (a.n - 1u) / 4u + 1u;  // n > 0
 #define RRT_GO(A, C) hipLaunchKernelGGL((RRT_WAVE_K(A, C)), dim3(grid), dim3(256), 0, stream, d_kp, a)
-    RRT_PICK(RRT_GO);
+#define RRT_GO_X(A, C) hipLaunchKernelGGL((RRT_WAVE_X(A, C)), dim3(grid), dim3(256), 0, stream, d_kp, a)
+    if (exit) RRT_PICK(RRT_GO_X); else RRT_PICK(RRT_GO);
 #undef RRT_GO
+#undef RRT_GO_X
   } else {
     const uint32_t grid = (a.n - 1u) / 256u + 1u;
 #define RRT_GO(A, C, K) hipLaunchKernelGGL((rrt_trace_lane_kernel<K, A, C>), dim3(grid), dim3(256), 0, stream, d_kp, a)
-    if (kerr) RRT_PICK(RRT_GO, true); else RRT_PICK(RRT_GO, false);
+#define RRT_GO_X(A, C, K) hipLaunchKernelGGL((rrt_trace_exit_lane_kernel<K, A, C>), dim3(grid), dim3(256), 0, stream, d_kp, a)
+    if (exit) { if (kerr) RRT_PICK(RRT_GO_X, true); else RRT_PICK(RRT_GO_X, false); }
+    else if (kerr) RRT_PICK(RRT_GO, true); else RRT_PICK(RRT_GO, false);
 #undef RRT_GO
+#undef RRT_GO_X
   }
 #undef RRT_PICK
 #undef RRT_WAVE_K
+#undef RRT_WAVE_X
   return hipGetLastError();
 }

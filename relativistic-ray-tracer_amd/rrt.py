@@ -11,6 +11,7 @@ Reference correspondence (pathtracer.h / pathtracer.cpp):
     .set_black_hole(c, r_s, dtheta)   the `-B` override of global_black_hole (main.cpp:139-145)
     .render(params, x0, y0, w, h)     raytrace_tile / raytrace_cell over a region (:549-609)
     .trace_rays(o, d) / .trace_camera BVHAccel::intersect itself, one first-hit record per ray (bvh.cpp:103-113)
+    .env_eval(dirs)                   EnvironmentLight::sample_dir (environment_light.cpp:146-148)
     RenderParams(...)                 AppConfig fields (application.h:41-85)
 """
 import ctypes as C
@@ -76,10 +77,12 @@ class EnvmapDesc(C.Structure):
 
 
 RRT_METRIC_SCHWARZSCHILD, RRT_METRIC_KERR = 0, 1
+RRT_SPACETIME_LENSED_SKY = 1  # rrt_spacetime_desc.flags
+RRT_SKY_FAR_M = 1000.0
 
 
 class SpacetimeDesc(C.Structure):
-    _fields_ = [("kind", C.c_uint32), ("reserved", C.c_uint32), ("center", C.c_double * 3), ("r_s", C.c_double),
+    _fields_ = [("kind", C.c_uint32), ("flags", C.c_uint32), ("center", C.c_double * 3), ("r_s", C.c_double),
                 ("delta_theta", C.c_double), ("spin", C.c_double), ("axis", C.c_double * 3)]
 
 
@@ -100,8 +103,8 @@ class Stats(C.Structure):
 
 
 # ray queries (include/rrt.h "ray queries")
-RRT_RAY_MISS, RRT_RAY_HIT, RRT_RAY_CAPTURED = 0, 1, 2
-RRT_TRACE_ANY_HIT = 1
+RRT_RAY_MISS, RRT_RAY_HIT, RRT_RAY_CAPTURED, RRT_RAY_ESCAPED = 0, 1, 2, 3
+RRT_TRACE_ANY_HIT, RRT_TRACE_EXIT = 1, 4  # (bit 1 is unassigned)
 RRT_TRACE_AUTO, RRT_TRACE_LANE_PER_RAY, RRT_TRACE_WAVE_PER_RAY = 0, 1, 2
 TRACE_MODES = {"auto": RRT_TRACE_AUTO, "lane": RRT_TRACE_LANE_PER_RAY, "wave": RRT_TRACE_WAVE_PER_RAY}
 RAY_DTYPE = np.dtype([("o", np.float64, 3), ("d", np.float64, 3)])  # rrt_ray, 48 bytes
@@ -113,9 +116,9 @@ class TraceParams(C.Structure):  # rrt_trace_params
     _fields_ = [("flags", C.c_uint32), ("mode", C.c_uint32), ("reserved", C.c_uint32 * 6)]
 
 
-def trace_params(any_hit=False, mode="auto"):
+def trace_params(any_hit=False, mode="auto", exit=False):
     p = TraceParams()
-    p.flags = RRT_TRACE_ANY_HIT if any_hit else 0
+    p.flags = (RRT_TRACE_ANY_HIT if any_hit else 0) | (RRT_TRACE_EXIT if exit else 0)
     p.mode = TRACE_MODES[mode] if isinstance(mode, str) else int(mode)
     return p
 
@@ -131,7 +134,7 @@ EXPORTS = ["rrt_abi_version", "rrt_create", "rrt_destroy", "rrt_last_error", "rr
            "rrt_exr_load", "rrt_exr_free", "rrt_exr_save", "rrt_kerr_frame", "rrt_get_big_masks",
            "rrt_get_occluders", "rrt_group_create", "rrt_group_render", "rrt_group_destroy", "rrt_libm_eval",
            "rrt_set_proof_audit", "rrt_get_proof_audit", "rrt_get_search_tree4", "rrt_trace_rays",
-           "rrt_trace_rays_device", "rrt_trace_camera", "rrt_trace_camera_device"]
+           "rrt_trace_rays_device", "rrt_trace_camera", "rrt_trace_camera_device", "rrt_env_eval"]
 AUDIT_KINDS = ("camera", "shadow", "pixel", "strip", "kerr", "zero")  # include/rrt.h RRT_AUDIT_*
 
 _lib = None
@@ -181,6 +184,8 @@ def lib():
         L.rrt_get_stats.argtypes = [vp, C.POINTER(Stats)]
         L.rrt_get_launch_times.argtypes = [vp, C.c_uint32, vp, vp]
         L.rrt_libm_eval.argtypes = [vp, C.c_int, vp, vp, vp, C.c_uint64]
+        if hasattr(L, "rrt_env_eval"):  # absent from older builds loaded through RRT_LIB
+            L.rrt_env_eval.argtypes = [vp, vp, C.c_uint64, vp]
         if hasattr(L, "rrt_set_proof_audit"):  # absent from older builds loaded through RRT_LIB
             L.rrt_set_proof_audit.argtypes = [vp, C.c_int]
             L.rrt_get_proof_audit.argtypes = [vp, vp]
@@ -413,10 +418,14 @@ class Renderer:
     def set_camera(self, cam):
         self._chk(lib().rrt_set_camera(self.h, C.byref(cam)))
 
-    def set_black_hole(self, center=(0.0, 1.0, 0.0), r_s=0.1, delta_theta=0.1, spin=None, axis=(0.0, 1.0, 0.0)):
+    def set_black_hole(self, center=(0.0, 1.0, 0.0), r_s=0.1, delta_theta=0.1, spin=None, axis=(0.0, 1.0, 0.0),
+                       lensed_sky=False):
         """The global black hole (-B).  spin=None: Schwarzschild (the reference's stepper);
-        spin=a/M in [0, 1): the Kerr integrator (build-defined) about `axis`."""
+        spin=a/M in [0, 1): the Kerr integrator (build-defined) about `axis`.
+        lensed_sky: escaping rays take the environment map along their exit direction and the
+        hole's shadow is black (RRT_SPACETIME_LENSED_SKY)."""
         st = SpacetimeDesc()
+        st.flags = RRT_SPACETIME_LENSED_SKY if lensed_sky else 0
         st.kind = RRT_METRIC_SCHWARZSCHILD if spin is None else RRT_METRIC_KERR
         st.center[0], st.center[1], st.center[2] = center
         st.r_s, st.delta_theta = r_s, delta_theta
@@ -446,6 +455,13 @@ class Renderer:
         self._chk(lib().rrt_libm_eval(self.h, self.LIBM_FN[fn], _p(a), _p(b), _p(out), a.size))
         return out
 
+    def env_eval(self, dirs):
+        """The device's EnvironmentLight::sample_dir on directions dirs [n, 3]: float32 [n, 3] (rrt_env_eval)."""
+        dirs = np.ascontiguousarray(np.asarray(dirs, np.float64).reshape(-1, 3))
+        out = np.zeros((len(dirs), 3), np.float32)
+        self._chk(lib().rrt_env_eval(self.h, _p(dirs), len(dirs), _p(out)))
+        return out
+
     def render(self, params, x0, y0, w, h, draws=False, counters=False):
         rgb = np.zeros((h, w, 3), np.float32)
         cnt = np.zeros((h, w), np.int32)
@@ -467,10 +483,12 @@ class Renderer:
     def tonemap_device(self, n, d_rgb, d_rgba, stream=None):
         self._chk(lib().rrt_tonemap_device(self.h, n, d_rgb, d_rgba, stream))
 
-    def trace_rays(self, o, d, any_hit=False, mode="auto"):
+    def trace_rays(self, o, d, any_hit=False, mode="auto", exit=False):
         """BVHAccel::intersect (bvh.cpp:103-113) of the rays (o [n, 3], d [n, 3]) under the context's
         spacetime: a structured array [n] with the layout of rrt_hit (HIT_DTYPE).  any_hit: the
-        shadow query (status and steps only).  mode: "auto", "lane" or "wave" (RRT_TRACE_*)."""
+        shadow query (status and steps only).  mode: "auto", "lane" or "wave" (RRT_TRACE_*).
+        exit: exit mode (RRT_TRACE_EXIT): an escaping ray's record is RRT_RAY_ESCAPED, w_out minus
+        its exit direction."""
         o = np.asarray(o, np.float64).reshape(-1, 3)
         d = np.asarray(d, np.float64).reshape(-1, 3)
         if len(o) != len(d):
@@ -478,24 +496,25 @@ class Renderer:
         rays = np.empty(len(o), RAY_DTYPE)
         rays["o"], rays["d"] = o, d
         hits = np.zeros(len(o), HIT_DTYPE)
-        self._chk(lib().rrt_trace_rays(self.h, C.byref(trace_params(any_hit, mode)), _p(rays), len(rays), _p(hits)))
+        self._chk(lib().rrt_trace_rays(self.h, C.byref(trace_params(any_hit, mode, exit)), _p(rays), len(rays), _p(hits)))
         return hits
 
-    def trace_camera(self, frame_w, frame_h, x0, y0, w, h, any_hit=False, mode="auto"):
+    def trace_camera(self, frame_w, frame_h, x0, y0, w, h, any_hit=False, mode="auto", exit=False):
         """The same query for the pixel-centre camera rays of a region of a frame_w x frame_h frame
         (raytrace_pixel's ray with ns_aa == 1): a structured array [h, w], y = 0 at the bottom."""
         hits = np.zeros((h, w), HIT_DTYPE)
-        self._chk(lib().rrt_trace_camera(self.h, C.byref(trace_params(any_hit, mode)), frame_w, frame_h, x0, y0, w, h,
+        self._chk(lib().rrt_trace_camera(self.h, C.byref(trace_params(any_hit, mode, exit)), frame_w, frame_h, x0, y0, w, h,
                                          _p(hits)))
         return hits
 
-    def trace_rays_device(self, d_rays, n, d_hits, any_hit=False, mode="auto", stream=None):
+    def trace_rays_device(self, d_rays, n, d_hits, any_hit=False, mode="auto", stream=None, exit=False):
         """Asynchronous form on device buffers (rrt_ray [n] -> rrt_hit [n], 16-byte aligned), like
         render_tiles_device."""
-        self._chk(lib().rrt_trace_rays_device(self.h, C.byref(trace_params(any_hit, mode)), d_rays, n, d_hits, stream))
+        self._chk(lib().rrt_trace_rays_device(self.h, C.byref(trace_params(any_hit, mode, exit)), d_rays, n, d_hits, stream))
 
-    def trace_camera_device(self, frame_w, frame_h, x0, y0, w, h, d_hits, any_hit=False, mode="auto", stream=None):
-        self._chk(lib().rrt_trace_camera_device(self.h, C.byref(trace_params(any_hit, mode)), frame_w, frame_h, x0, y0,
+    def trace_camera_device(self, frame_w, frame_h, x0, y0, w, h, d_hits, any_hit=False, mode="auto", stream=None,
+                            exit=False):
+        self._chk(lib().rrt_trace_camera_device(self.h, C.byref(trace_params(any_hit, mode, exit)), frame_w, frame_h, x0, y0,
                                                 w, h, d_hits, stream))
 
     def stats(self):
