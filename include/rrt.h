@@ -149,6 +149,32 @@ enum { RRT_SPACETIME_LENSED_SKY = 1u << 0 };
  * RRT_METRIC_KERR swaps BlackHole::next_micro_ray for an RK4 null-geodesic step in Kerr-Schild
  * coordinates; the rest of BVHAccel::intersect (segment tests, capture = no hit) is unchanged. */
 int rrt_set_spacetime(rrt_ctx* ctx, const rrt_spacetime_desc* st);
+/* Thin accretion disk of a Kerr hole (build-defined): the annulus r_in <= r <= r_out
+ * (Boyer-Lindquist r, in units of M) of the hole's equatorial plane; opaque, infinitely thin,
+ * emitting, on prograde circular geodesics.  The Kerr march tests every step for a crossing of the
+ * plane; a camera ray that reaches the disk returns emission x (r_in / r)^3 x g^4, g the redshift
+ * from the photon's L_z at the crossing; every other ray that reaches it ends there (a shadow ray is
+ * occluded; the radiance enters where a hit's emission does: hemisphere-sampled direct light and
+ * the bounce after a delta BSDF).  The disk is no light: it is not importance-sampled.
+ * Rendered by one build of the general per-pixel-loop kernel (any depth, every ray marched exactly,
+ * no proofs; with or without RRT_SPACETIME_LENSED_SKY).  At render or trace time RRT_E_INVALID for a
+ * Schwarzschild-kind spacetime (its stepper carries no momentum: take RRT_METRIC_KERR with spin
+ * 0), for an r_in below the prograde ISCO of the current spin, and, rendering, with
+ * RRT_RENDER_WAVEFRONT, RRT_RENDER_DEEP_SAMPLE, RRT_RENDER_COUNTERS or the reference's switch
+ * flags.  The members of a group share the disk as they share the spacetime.  Without a disk every
+ * output is what it was. */
+enum { RRT_DISK_NO_REDSHIFT = 1u << 0 };  /* g = 1: the bare (r_in / r)^3 profile */
+typedef struct {
+  double r_in, r_out;         /* in M; r_in == 0: the prograde ISCO of the spin in force at launch */
+  float emission[3];          /* radiance at r = r_in for g = 1 */
+  uint32_t flags;             /* RRT_DISK_* */
+  uint32_t reserved[4];
+} rrt_disk_desc;
+/* NULL removes the disk.  RRT_E_INVALID: a non-finite or negative value, r_out <= r_in, unknown flags. */
+int rrt_set_disk(rrt_ctx* ctx, const rrt_disk_desc* disk);
+/* 1 and the disk in force (r_in resolved against the current spacetime: 0 -> the ISCO radius in M
+ * if the spacetime is Kerr), or 0 without a disk; works on a host-only context. */
+int rrt_get_disk(const rrt_ctx* ctx, rrt_disk_desc* out);
 /* The validated envelope of the camera / pixel / shadow proofs (profiles/
  * r03_proof_sweep.json): delta_theta in [RRT_PROOF_DT_MIN, RRT_PROOF_DT_MAX] and r_s <=
  * RRT_PROOF_RS_OVER_EXTENT x the scene's largest root-box extent.  Outside it the kernels march
@@ -349,8 +375,17 @@ enum { RRT_RAY_MISS = 0,      /* the march ended with neither: the Schwarzschild
        RRT_RAY_HIT = 1,
        RRT_RAY_CAPTURED = 2,  /* the capture test (bvh.cpp:107; Kerr: the horizon test) fired
                                  before any hit */
-       RRT_RAY_ESCAPED = 3 }; /* RRT_TRACE_EXIT only: the ray left the scene for good; w_out is minus
+       RRT_RAY_ESCAPED = 3,   /* RRT_TRACE_EXIT only: the ray left the scene for good; w_out is minus
                                  its exit direction, every other hit field 0 / -1 */
+       RRT_RAY_DISK = 4 };    /* with a disk set (rrt_set_disk) only: the ray reached
+                                 the accretion disk before any hit.  hit_p: the world crossing point;
+                                 w_out: minus the crossing step's chord direction; t: along that
+                                 chord; steps: the crossing step's index + 1; prim = bsdf = -1;
+                                 n: the world unit normal +-ez on the side the ray came from, scaled
+                                 by the redshift g (|n| = g; 1 with RRT_DISK_NO_REDSHIFT).  On the
+                                 crossing step a primitive hit wins iff its t <= the disk's; a
+                                 capture wins always.  Lane per ray; combines with RRT_TRACE_EXIT
+                                 and RRT_TRACE_ANY_HIT (status and steps alone). */
 typedef struct {              /* 96 bytes; without a closest hit every field but status and steps
                                  is 0, prim and bsdf -1 */
   double hit_p[3];            /* Intersection::hit_p */

@@ -66,6 +66,8 @@ class PathTracer {
   // the lensed sky (RRT_SPACETIME_LENSED_SKY): escaping rays see the environment map
   // along their exit direction, the hole's shadow is black
   void set_lensed_sky(bool on);
+  // the thin accretion disk of a Kerr hole (rrt_set_disk); nullptr removes it
+  void set_disk(const rrt_disk_desc* disk);
   void set_seed(uint64_t seed) { seed_ = seed; }  // keyed RNG seed
   void set_band_rows(size_t rows) { band_rows_ = rows; }  // rows per GPU submission (0: whole region)
 

@@ -7,7 +7,9 @@
 //   -b R  lens radius  -d D  focal distance  -B X Y Z R DTHETA  black hole (centre, r_s, step)
 // plus --seed S (keyed RNG seed), --device D and --kerr A [AX AY AZ] (Kerr spin a/M about the
 // axis, default +y; build-defined) and --lensed-sky (escaping rays see the environment
-// map along their exit direction).  The interactive viewer is out of scope: -f is
+// map along their exit direction) and --disk R_IN R_OUT [--disk-emission R G B]
+// [--disk-no-redshift] (a thin accretion disk, radii in M, R_IN 0 = the ISCO; needs --kerr; DESIGN.md
+// §12).  The interactive viewer is out of scope: -f is
 // required.  Exit codes follow main.cpp (usage -> 1).
 #include <cstdio>
 #include <cstdlib>
@@ -38,6 +40,8 @@ static void usage(const char* binary) {
   std::printf("  --devices <D0,D1,...>  Render on several GPUs (block-cyclic tiles, RCCL gather)\n");
   std::printf("  --kerr <A> [<AX> <AY> <AZ>]  Kerr black hole, spin a/M in [0,1) about axis (default 0 1 0)\n");
   std::printf("  --lensed-sky     Look the environment map up along the bent ray; the hole's shadow is black\n");
+  std::printf("  --disk <R_IN> <R_OUT>  Thin accretion disk, radii in M (R_IN 0: the ISCO); needs --kerr\n");
+  std::printf("  --disk-emission <R> <G> <B>  Disk radiance at R_IN (default 1 1 1)   --disk-no-redshift  g = 1\n");
   std::printf("  -h               Print this help message\n");
 }
 
@@ -54,7 +58,10 @@ int main(int argc, char** argv) {
   unsigned long long seed = 0;
   int device = 0;
   std::vector<int> devices;  // --devices: several GPUs (rrt_group)
-  bool to_file = false, lensed_sky = false;
+  bool to_file = false, lensed_sky = false, has_disk = false;
+  rrt_disk_desc disk;
+  std::memset(&disk, 0, sizeof(disk));
+  disk.emission[0] = disk.emission[1] = disk.emission[2] = 1.0f;
   auto need = [&](int i, int n) {
     if (i + n >= argc) { usage(argv[0]); std::exit(1); }
   };
@@ -98,6 +105,16 @@ int main(int argc, char** argv) {
       device = devices[0];
     }
     else if (a == "--lensed-sky") { lensed_sky = true; }
+    else if (a == "--disk") {
+      need(i, 2);
+      disk.r_in = std::atof(argv[++i]); disk.r_out = std::atof(argv[++i]);
+      has_disk = true;
+    }
+    else if (a == "--disk-emission") {
+      need(i, 3);
+      for (int k = 0; k < 3; ++k) disk.emission[k] = (float)std::atof(argv[++i]);
+    }
+    else if (a == "--disk-no-redshift") { disk.flags |= RRT_DISK_NO_REDSHIFT; }
     else if (a == "--kerr") {
       need(i, 1);
       kerr_spin = std::atof(argv[++i]);
@@ -160,6 +177,7 @@ int main(int argc, char** argv) {
   pt.set_black_hole(hole, hole[3], hole[4]);
   if (kerr_spin >= 0) pt.set_kerr(kerr_spin, kerr_axis);
   if (lensed_sky) pt.set_lensed_sky(true);
+  if (has_disk) pt.set_disk(&disk);
   // Application::set_up_pathtracer (application.cpp:622-628)
   pt.set_camera(&camera);
   pt.set_scene(scene);

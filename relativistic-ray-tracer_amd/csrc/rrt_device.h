@@ -286,6 +286,13 @@ struct ExitRec {
   v3 e;
   bool escaped;
 };
+// What a disk-build march (kerr_march with DISK) reports when the ray ended on the
+// accretion disk: hit, and then the radiance it sees there (the Isect carries the crossing point, minus
+// the chord's direction and the g-scaled normal; bsdf = -1).  A shadow query fills hit alone.
+struct DiskRec {
+  spec rgb;
+  bool hit;
+};
 
 // BVHAccel::intersect_micro (bvh.cpp:115-138) for one micro segment.  ANY: shadow query, stop
 // at the first accepted primitive (only the boolean is used; result-identical).
@@ -840,10 +847,16 @@ __device__ __forceinline__ uint32_t sw_illum(const KParams& kp) { return ((kp.sw
 // exit direction.  Per-pixel-loop kernel only (rrt_kernel.hip); no proofs.
 constexpr int V_SKY = 5;
 constexpr int V_KERR_SKY = 6;
+// V_KERR_DISK: the general Kerr build with the accretion disk (rrt_set_disk).  It carries
+// the exit-mode march and takes the lensed sky's rule or the reference's at run time (kp.disk.lensed).
+// Per-pixel-loop kernel only; no proofs.
+constexpr int V_KERR_DISK = 7;
 __host__ __device__ constexpr bool is_lean(int v) { return v == 1 || v == 2; }
 __host__ __device__ constexpr bool is_sky(int v) { return v == V_SKY || v == V_KERR_SKY; }
-__host__ __device__ constexpr bool is_kerr_build(int v) { return v == V_KERR || v == V_KERR_SKY; }
-__host__ __device__ constexpr int general_of(int v) { return v == V_KERR || v == V_SW || is_sky(v) ? v : 0; }  // non-LEAN build
+__host__ __device__ constexpr bool is_kerr_build(int v) { return v == V_KERR || v == V_KERR_SKY || v == V_KERR_DISK; }
+__host__ __device__ constexpr int general_of(int v) {  // non-LEAN build
+  return v == V_KERR || v == V_SW || is_sky(v) || v == V_KERR_DISK ? v : 0;
+}
 
 // ------------------------------------------------------------------ Kerr (build-defined)
 // The reference has no Kerr metric; this integrator is this build's design
@@ -1005,9 +1018,9 @@ __device__ __forceinline__ void audit_note(const KParams& kp, int k, bool violat
   if (violated) atomicAdd(kp.audit + 2 * k + 1, 1ull);
 }
 __device__ __forceinline__ bool kerr_occluded_proof(const KParams& kp, v3 o, v3 d);
-template <bool ANY, bool COUNT, bool EXIT = false>
+template <bool ANY, bool COUNT, bool EXIT = false, bool DISK = false>
 __device__ __forceinline__ bool kerr_march(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn, QRec* qr = nullptr,
-                                           ExitRec* xr = nullptr);
+                                           ExitRec* xr = nullptr, DiskRec* dk = nullptr);
 template <bool ANY, bool COUNT>
 __device__ __forceinline__ bool query_kerr(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn) {
   // shadow rays: the occlusion proof first (never in the reference-work counts)
@@ -1048,9 +1061,51 @@ __device__ __forceinline__ void kerr_far_march(const DHole& h, v3 q, v3 p, v3 a,
     q = q1; p = p1;
   }
 }
-// the march of query_kerr (no proof).  EXIT: an escaping photon goes on to its exit direction (*xr)
-template <bool ANY, bool COUNT, bool EXIT>
-__device__ __forceinline__ bool kerr_march(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn, QRec* qr, ExitRec* xr) {
+// The accretion disk: the annulus r_in <= r <= r_out of the local plane z = 0, where
+// r^2 = x^2 + y^2 - a^2.  A step (q0, p0) -> (q1, p1) crosses the plane iff z changes sign or ends on
+// it (NaN: no crossing), at the fraction s of the step; position and covector are interpolated
+// linearly.  True iff the crossing point lies on the annulus; s and the point's x, y out.
+__device__ __forceinline__ bool disk_cross(const DHole& h, const DDisk& dd, v3 q0, v3 q1, double& s, double& x, double& y) {
+  if (!((q0.z > 0.0 && q1.z <= 0.0) || (q0.z < 0.0 && q1.z >= 0.0))) return false;
+  s = xdiv(q0.z, q0.z - q1.z);
+  x = q0.x + s * (q1.x - q0.x);
+  y = q0.y + s * (q1.y - q0.y);
+  const double r2 = (x * x + y * y) - h.a2;
+  return r2 >= dd.r_in2 && r2 <= dd.r_out2;
+}
+// Redshift and radiance at a crossing (once per ray: + - x / sqrt only, correctly rounded).  The gas
+// moves on the prograde circular geodesic of radius r: Omega = sqrt(M) / (r^1.5 + k), k = a sqrt(M),
+// u^t = (1 + k / r^1.5) / sqrt(1 - 3M / r + 2k / r^1.5).  The march's photon has E = 1 (p_t = -1) and
+// L_z = x p_y - y p_x, so g = E_observed / E_emitted = 1 / (u^t (1 - Omega L_z)), the observer's own
+// constant factor left out; a g that is not finite and positive counts as 0.  The radiance is
+// emission x (r_in / r)^3 x g^4 (bolometric).  g out.
+__device__ __forceinline__ spec disk_radiance(const DHole& h, const DDisk& dd, double x, double y, double lz, double& g_out) {
+  const double r = xsqrt((x * x + y * y) - h.a2);
+  double g = 1.0;
+  if (!dd.no_redshift) {
+    const double r32 = r * xsqrt(r);
+    const double kr = xdiv(dd.k, r32);
+    const double om = xdiv(dd.sqrt_m, r32 + dd.k);
+    const double ut = xdiv(1.0 + kr, xsqrt((1.0 - xdiv(3.0 * h.m, r)) + 2.0 * kr));
+    g = xdiv(1.0, ut * (1.0 - om * lz));
+    if (!(g > 0.0 && isfinite(g))) g = 0.0;
+  }
+  const double c = xdiv(dd.r_in, r);
+  double w = (c * c) * c;
+  if (!dd.no_redshift) {
+    const double g2 = g * g;
+    w = w * (g2 * g2);
+  }
+  g_out = g;
+  return S(dd.emission[0] * (float)w, dd.emission[1] * (float)w, dd.emission[2] * (float)w);
+}
+// the march of query_kerr (no proof).  EXIT: an escaping photon goes on to its exit direction (*xr).
+// DISK: with kp.disk.on every step is tested against the accretion disk next to its chord's segment
+// query: a capture wins; else the chord's closest primitive hit wins iff its
+// t <= t_disk = s max_t, else the disk (*dk; the Isect and qr->t as for a hit, bsdf and slot -1).
+template <bool ANY, bool COUNT, bool EXIT, bool DISK>
+__device__ __forceinline__ bool kerr_march(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn, QRec* qr, ExitRec* xr,
+                                           DiskRec* dk) {
   const DHole& h = kp.hole;
   v3 q, p;
   kerr_init(h, o, d, q, p);
@@ -1059,6 +1114,7 @@ __device__ __forceinline__ bool kerr_march(const KParams& kp, v3 o, v3 d, Isect*
   double swept = 0.0;
   int j = 0;
   for (; j < h.kerr_max_steps && swept < 2.0 * PI_D; ++j) {
+    const v3 q0 = q, p0 = p;  // DISK: the step's start
     v3 q1 = q, p1 = p;
     double sw1 = swept;
     KArith<true> fast;
@@ -1084,7 +1140,47 @@ __device__ __forceinline__ bool kerr_march(const KParams& kp, v3 o, v3 d, Isect*
     const double max_t = norm(seg);
     const double inv = xdiv(1., max_t);
     const v3 sd = V(seg.x * inv, seg.y * inv, seg.z * inv);  // normalize(seg), norm shared
-    if (segment_query<ANY, COUNT, false>(kp, a, sd, max_t, a + vmul(sd, max_t), is, cn, false, qr)) return true;
+    if (DISK) {
+      // one walk per chord: a closest-hit march compares its own walk's hit with the disk afterwards
+      double s = 0.0, x = 0.0, y = 0.0;
+      const bool cross = kp.disk.on && disk_cross(h, kp.disk, q0, q, s, x, y);
+      const double t_disk = s * max_t;
+      // the interpolated covector's L_z = x p_y - y p_x, before the walk: the step's start state dies here
+      const double lz = x * (p0.y + s * (p.y - p0.y)) - y * (p0.x + s * (p.x - p0.x));
+      const bool above = q0.z > 0.0;  // the side the ray came from
+      QRec lq = {-1, 0.0, 0u, false};
+      QRec* const q2 = qr ? qr : &lq;
+      if (ANY) {
+        if (cross) {
+          if (dk) dk->hit = true;
+          if (!qr) return true;  // a shadow ray is occluded by either
+          // a shadow query's status is the closest-hit query's: the chord's closest hit decides
+          Isect li;
+          if (segment_query<false, COUNT, false>(kp, a, sd, max_t, a + vmul(sd, max_t), &li, cn, false, q2) &&
+              q2->t <= t_disk && dk)
+            dk->hit = false;
+          return true;
+        }
+        if (segment_query<true, COUNT, false>(kp, a, sd, max_t, a + vmul(sd, max_t), is, cn, false, qr)) return true;
+      } else {
+        const bool prim = segment_query<false, COUNT, false>(kp, a, sd, max_t, a + vmul(sd, max_t), is, cn, false, q2);
+        if (prim && !(cross && q2->t > t_disk)) return true;
+        if (cross) {
+          double g;
+          const spec rgb = disk_radiance(h, kp.disk, x, y, lz, g);
+          if (dk) { dk->hit = true; dk->rgb = rgb; }
+          const double gs = above ? g : -g;
+          is->hit_p = a + vmul(sd, t_disk);
+          is->w_out = -sd;
+          is->n = V(h.ez[0] * gs, h.ez[1] * gs, h.ez[2] * gs);
+          is->bsdf = -1;
+          q2->slot = -1; q2->t = t_disk;
+          return true;
+        }
+      }
+    } else if (segment_query<ANY, COUNT, false>(kp, a, sd, max_t, a + vmul(sd, max_t), is, cn, false, qr)) {
+      return true;
+    }
     a = b;
   }
   return false;
@@ -1331,10 +1427,11 @@ __device__ __forceinline__ bool shadow_occluded_proof(const KParams& kp, v3 o, v
 // EXIT: the exit-mode march (no proofs): the Schwarzschild march stops at the escape
 // row -- that row's capture test and walk, and every later row, are not run -- and *xr (if given)
 // says whether and where the ray escaped; Kerr: kerr_march's far march.
-template <bool ANY, bool COUNT, bool KERR = false, bool W4 = true, bool EXIT = false>
+// DISK (Kerr exit-mode builds): the march tests the accretion disk too (kerr_march; *dk)
+template <bool ANY, bool COUNT, bool KERR = false, bool W4 = true, bool EXIT = false, bool DISK = false>
 RRT_QUERY_ATTR bool query(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn, bool any_rt = false,
-                          QRec* qr = nullptr, ExitRec* xr = nullptr) {
-  if (KERR && EXIT) return kerr_march<ANY, COUNT, true>(kp, o, d, is, cn, qr, xr);
+                          QRec* qr = nullptr, ExitRec* xr = nullptr, DiskRec* dk = nullptr) {
+  if (KERR && EXIT) return kerr_march<ANY, COUNT, true, DISK>(kp, o, d, is, cn, qr, xr, dk);
   if (KERR) return qr ? kerr_march<ANY, COUNT>(kp, o, d, is, cn, qr) : query_kerr<ANY, COUNT>(kp, o, d, is, cn);
   if (qr) qr->steps = (uint32_t)kp.hole.steps;  // all marched, unless a segment below ends the march
   if (COUNT && !kp.count_exec && !(kp.diag & 2)) cn.query++;

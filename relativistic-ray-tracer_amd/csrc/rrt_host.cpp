@@ -38,6 +38,7 @@ hipError_t rrt_launch_path(const KParams* d_kp, int waves, uint32_t grid, hipStr
 hipError_t rrt_launch_env(const DEnv& env, uint64_t n, const double* dirs, float* rgb, hipStream_t stream);
 hipError_t rrt_launch_trace(const KParams* d_kp, const TraceArgs& a, int kerr, int any, int exit, int mode, int n_cu, int* mode_out,
                             hipStream_t stream);
+hipError_t rrt_launch_trace_disk(const KParams* d_kp, const TraceArgs& a, int any, int exit, hipStream_t stream);
 hipError_t rrt_launch_unpack(const uint32_t* tiles, uint32_t n_tiles, uint32_t ts, uint32_t fw, uint32_t fh,
                              const float* rgb_p, const int32_t* cnt_p, float* rgb, int32_t* cnt, hipStream_t stream);
 hipError_t rrt_launch_libm(int fn, uint64_t n, const double* a, const double* b, double* out, hipStream_t stream);
@@ -170,6 +171,8 @@ struct rrt_ctx {
   double lens_r = 0.0, focal = 0.0;  // Camera::lensRadius / focalDistance (thin lens, RRT_RENDER_THIN_LENS)
   DHole hole{};
   bool lensed_sky = false;  // RRT_SPACETIME_LENSED_SKY
+  bool has_disk = false;    // rrt_set_disk; r_in == 0: the ISCO, resolved at launch
+  rrt_disk_desc disk{};
   // device scene
   DNode* d_nodes = nullptr;
   DPrimGeo* d_geo = nullptr;
@@ -1264,6 +1267,77 @@ extern "C" int rrt_set_spacetime(rrt_ctx* c, const rrt_spacetime_desc* st) {
   return RRT_OK;
 }
 
+// ---------------------------------------------------------------- accretion disk
+// Prograde ISCO radius in M of a Kerr hole of spin s = a/M (Bardeen, Press & Teukolsky 1972, eq. 2.21)
+static double kerr_isco(double s) {
+  const double z1 = 1.0 + std::cbrt(1.0 - s * s) * (std::cbrt(1.0 + s) + std::cbrt(1.0 - s));
+  const double z2 = std::sqrt(3.0 * s * s + z1 * z1);
+  return 3.0 + z2 - std::sqrt((3.0 - z1) * (3.0 + z1 + 2.0 * z2));
+}
+static double hole_spin(const DHole& h) { return h.m > 0.0 ? h.a / h.m : 0.0; }
+
+extern "C" int rrt_set_disk(rrt_ctx* c, const rrt_disk_desc* d) {
+  if (!c) return RRT_E_INVALID;
+  if (!d) { c->has_disk = false; c->disk = rrt_disk_desc{}; return RRT_OK; }
+  if (!(std::isfinite(d->r_in) && std::isfinite(d->r_out) && d->r_in >= 0.0 && d->r_out >= 0.0))
+    return fail(c, RRT_E_INVALID, "disk radii must be finite and >= 0");
+  for (int k = 0; k < 3; ++k)
+    if (!(std::isfinite(d->emission[k]) && d->emission[k] >= 0.0f))
+      return fail(c, RRT_E_INVALID, "disk emission must be finite and >= 0");
+  if (!(d->r_out > d->r_in)) return fail(c, RRT_E_INVALID, "disk needs r_out > r_in");
+  if (d->flags & ~(uint32_t)RRT_DISK_NO_REDSHIFT) return fail(c, RRT_E_INVALID, "unknown rrt_disk_desc flags");
+  c->disk = *d;
+  for (uint32_t& r : c->disk.reserved) r = 0u;
+  c->has_disk = true;
+  return RRT_OK;
+}
+
+extern "C" int rrt_get_disk(const rrt_ctx* c, rrt_disk_desc* out) {
+  if (!c || !c->has_disk) return 0;
+  if (out) {
+    *out = c->disk;
+    if (out->r_in == 0.0 && c->hole.kind == RRT_METRIC_KERR) out->r_in = kerr_isco(hole_spin(c->hole));
+  }
+  return 1;
+}
+
+// The disk of a render or trace launch: validated against the spacetime in force, r_in resolved, the
+// device constants filled and the escape radius widened to hold it (the far march tests no disk).
+// Call with kp.hole filled (fill_scene_params).  Without a disk: RRT_OK, kp untouched.
+static int fill_disk_params(rrt_ctx* c, KParams& kp) {
+  if (!c->has_disk) return RRT_OK;
+  if (c->hole.kind != RRT_METRIC_KERR)
+    return fail(c, RRT_E_INVALID, "the accretion disk needs the Kerr march (the Schwarzschild stepper carries no photon "
+                                  "momentum): set RRT_METRIC_KERR with spin 0");
+  const DHole& h = kp.hole;
+  const double isco = kerr_isco(hole_spin(h));
+  const double r_in = c->disk.r_in == 0.0 ? isco : c->disk.r_in;
+  if (r_in < isco) return fail(c, RRT_E_INVALID, "disk r_in lies below the prograde ISCO of the current spin");
+  if (!(c->disk.r_out > r_in)) return fail(c, RRT_E_INVALID, "disk needs r_out > r_in (the ISCO of the current spin)");
+  DDisk& d = kp.disk;
+  d.r_in = r_in * h.m;
+  d.r_in2 = d.r_in * d.r_in;
+  const double r_out = c->disk.r_out * h.m;
+  d.r_out2 = r_out * r_out;
+  d.sqrt_m = std::sqrt(h.m);
+  d.k = h.a * d.sqrt_m;
+  for (int k = 0; k < 3; ++k) d.emission[k] = c->disk.emission[k];
+  d.on = 1u;
+  d.no_redshift = (c->disk.flags & RRT_DISK_NO_REDSHIFT) ? 1u : 0u;
+  d.lensed = c->lensed_sky ? 1u : 0u;
+  const double e2 = d.r_out2 + h.a2;  // |q|^2 on the plane at r_out
+  if (e2 > kp.hole.r_esc2) kp.hole.r_esc2 = e2;
+  return RRT_OK;
+}
+
+// the disk against the spacetime in force, with no launch at hand
+static int check_disk(rrt_ctx* c) {
+  if (!c->has_disk) return RRT_OK;
+  KParams probe{};
+  probe.hole = c->hole;
+  return fill_disk_params(c, probe);
+}
+
 extern "C" void rrt_kerr_frame(const double* axis, double* ex, double* ey, double* ez) {
   // ez = unit(axis); ex = unit(t x ez) with t the world axis least aligned with ez; ey = ez x ex
   const double n = std::sqrt(axis[0] * axis[0] + axis[1] * axis[1] + axis[2] * axis[2]);
@@ -1419,6 +1493,7 @@ static int launch(rrt_ctx* c, const rrt_render_params* p, const uint32_t* tiles,
                   uint32_t* d_draws, uint32_t* d_ctr, hipStream_t stream) {
   if (!c->has_scene) return fail(c, RRT_E_INVALID, "no scene (rrt_set_scene)");
   if (!c->has_camera) return fail(c, RRT_E_INVALID, "no camera (rrt_set_camera)");
+  if (int rc = check_disk(c)) return rc;  // before any device work
   if (c->device < 0) return fail(c, RRT_E_NO_DEVICE, "host-only context cannot render");
   if (p->frame_w == 0 || p->frame_h == 0) return fail(c, RRT_E_INVALID, "frame size is zero");
   if (p->samples_per_batch == 0) return fail(c, RRT_E_INVALID, "samples_per_batch must be > 0");
@@ -1579,6 +1654,15 @@ static int launch(rrt_ctx* c, const rrt_render_params* p, const uint32_t* tiles,
                                   "not with RRT_RENDER_WAVEFRONT, RRT_RENDER_DEEP_SAMPLE, RRT_RENDER_COUNTERS or the "
                                   "reference's switch flags");
   if (sky) { kp.miss.on = 0u; kp.occ.on = 0u; kp.kproof.on = 0u; }
+  // the accretion disk (rrt_set_disk): the general per-pixel-loop build V_KERR_DISK
+  // (rrt_kernel.hip), every query the exit-mode march with the disk test, no proof; the lensed sky's rule
+  const bool disk = c->has_disk;
+  if (disk && (sw || (p->flags & (RRT_RENDER_WAVEFRONT | RRT_RENDER_DEEP_SAMPLE | RRT_RENDER_COUNTERS))))
+    return fail(c, RRT_E_INVALID, "the accretion disk (rrt_set_disk) renders in the per-pixel-loop kernel only: not with "
+                                  "RRT_RENDER_WAVEFRONT, RRT_RENDER_DEEP_SAMPLE, RRT_RENDER_COUNTERS or the reference's "
+                                  "switch flags");
+  if (int rc = fill_disk_params(c, kp)) return rc;
+  if (disk) { kp.miss.on = 0u; kp.occ.on = 0u; kp.kproof.on = 0u; }
   // bounce paths (depth >= 2): the per-pixel-loop kernel by default; RRT_RENDER_DEEP_SAMPLE selects
   // the per-sample refill kernel (rrt_sample.hip, one lane per pixel, a lane whose pixel is done
   // takes the next at the next sample boundary) -- m3 A/B, profiles/r03_ab_deep.jsonl: 177 ms
@@ -1597,8 +1681,9 @@ static int launch(rrt_ctx* c, const rrt_render_params* p, const uint32_t* tiles,
                      (uint64_t)all_lights(c).size() * std::max<uint32_t>(1u, p->ns_area_light) < 2048u))
     return fail(c, RRT_E_INVALID, "RRT_RENDER_WAVEFRONT (the path pool kernel) renders max_ray_depth >= 2 "
                                   "Schwarzschild frames without counters or switches, n_lights x ns_area_light < 2048");
-  const bool pixel_loop = !path_pool && ((deep && !deep_sample) || (p->flags & RRT_RENDER_PIXEL_LOOP) || sw || sky);
-  const int lean = sky ? (kerr ? 6 /* V_KERR_SKY */ : 5 /* V_SKY */)
+  const bool pixel_loop = !path_pool && ((deep && !deep_sample) || (p->flags & RRT_RENDER_PIXEL_LOOP) || sw || sky || disk);
+  const int lean = disk ? 7 /* V_KERR_DISK */
+                 : sky ? (kerr ? 6 /* V_KERR_SKY */ : 5 /* V_SKY */)
                  : kerr ? 3 /* V_KERR */
                  : sw ? 4 /* V_SW */
                  : (!deep && !count && !c->env_w && !p->direct_hemisphere) ? c->lean : 0;
@@ -1975,7 +2060,7 @@ static int launch(rrt_ctx* c, const rrt_render_params* p, const uint32_t* tiles,
     HIPCHK(c, rrt_launch_path(c->d_kp, waves, grid, stream));
   } else if (pixel_loop) {
     std::snprintf(name, sizeof(name), "%srrt_render_kernel<%s, %s, %d, ...>", deep_list ? "rrt_pixel_proof_kernel + " : "",
-                  tf[deep || sw || sky], tf[count], lean == 2 ? 0 : lean);
+                  tf[deep || sw || sky || disk], tf[count], lean == 2 ? 0 : lean);
     if (deep_list) HIPCHK(c, rrt_launch_pixel_proof(c->d_kp, kp.n_pixels, kp.strip_list != nullptr, stream));
     HIPCHK(c, hipEventRecord(c->ev_main[ring], stream));
     HIPCHK(c, rrt_launch_render(kp, c->d_kp, deep, count, lean, waves, grid, stream));
@@ -2120,6 +2205,7 @@ static int trace_launch(rrt_ctx* c, const rrt_trace_params* tp, bool cam, const 
   const bool kerr = c->hole.kind == RRT_METRIC_KERR;
   if (kerr && mode == RRT_TRACE_WAVE_PER_RAY)
     return fail(c, RRT_E_INVALID, "RRT_TRACE_WAVE_PER_RAY walks the Schwarzschild stepper's chain only (Kerr: lane per ray)");
+  if (int rc = check_disk(c)) return rc;  // before any device work
   if (c->device < 0) return fail(c, RRT_E_NO_DEVICE, "host-only context cannot trace");
   if (n == 0) return RRT_OK;
   if (!d_hits || (!cam && !d_rays)) return fail(c, RRT_E_INVALID, "null argument");
@@ -2134,12 +2220,17 @@ static int trace_launch(rrt_ctx* c, const rrt_trace_params* tp, bool cam, const 
   fill_scene_params(c, 0u, kp);
   kp.frame_w = (double)fw; kp.frame_h = (double)fh;
   kp.frame_wi = fw; kp.frame_hi = fh;
+  if (int rc = fill_disk_params(c, kp)) return rc;
   HIPCHK(c, hipMemcpyAsync(c->d_kp, &kp, sizeof(KParams), hipMemcpyHostToDevice, stream));
   TraceArgs a{};
   a.rays = cam ? nullptr : reinterpret_cast<const double*>(d_rays);
   a.hits = d_hits;
   a.slot_prim = c->d_leaf;
   a.n = n; a.x0 = x0; a.y0 = y0; a.w = w ? w : 1u;
+  if (c->has_disk) {  // the disk builds (Kerr, lane per ray)
+    HIPCHK(c, rrt_launch_trace_disk(c->d_kp, a, (flags & RRT_TRACE_ANY_HIT) ? 1 : 0, (flags & RRT_TRACE_EXIT) ? 1 : 0, stream));
+    return RRT_OK;
+  }
   HIPCHK(c, rrt_launch_trace(c->d_kp, a, kerr ? 1 : 0, (flags & RRT_TRACE_ANY_HIT) ? 1 : 0, (flags & RRT_TRACE_EXIT) ? 1 : 0, (int)mode, c->n_cu, nullptr,
                              stream));
   return RRT_OK;
@@ -2223,6 +2314,7 @@ extern "C" int rrt_render(rrt_ctx* c, const rrt_render_params* p, uint32_t x0, u
   if (!c || !p || !rgb_out || !count_out) return fail(c, RRT_E_INVALID, "null argument");
   if (w == 0 || h == 0) return RRT_OK;
   if ((uint64_t)x0 + w > p->frame_w || (uint64_t)y0 + h > p->frame_h) return fail(c, RRT_E_INVALID, "region outside frame");
+  if (int rc = check_disk(c)) return rc;
   if (c->device < 0) return fail(c, RRT_E_NO_DEVICE, "host-only context cannot render");
   if (cancel && *cancel) return fail(c, RRT_E_CANCELLED, "cancelled");
   HIPCHK(c, hipSetDevice(c->device));
@@ -2646,6 +2738,10 @@ extern "C" int rrt_group_render(rrt_group* g, const rrt_render_params* p, uint32
   if ((uint64_t)x0 + w > p->frame_w || (uint64_t)y0 + h > p->frame_h)
     return group_fail(g, RRT_E_INVALID, "region outside frame");
   const uint32_t n = (uint32_t)g->ctx.size(), ts = 32, T2 = ts * ts;
+  for (uint32_t i = 1; i < n; ++i)  // the members share the disk, as they share the spacetime
+    if (g->ctx[i]->has_disk != g->ctx[0]->has_disk ||
+        (g->ctx[0]->has_disk && std::memcmp(&g->ctx[i]->disk, &g->ctx[0]->disk, sizeof(rrt_disk_desc)) != 0))
+      return group_fail(g, RRT_E_INVALID, "the members of a group must share the accretion disk (rrt_set_disk)");
   if (g->distinct && g->comm.empty())
     return group_fail(g, RRT_E_HIP, "the group's RCCL communicators were aborted after a failed gather");
   // the region's tiles, dealt over the members as a lattice (rrt_region_tiles)

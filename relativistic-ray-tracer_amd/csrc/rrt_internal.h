@@ -170,6 +170,18 @@ __host__ __device__ __forceinline__ uint32_t claim_r(uint32_t c, uint32_t ts) {
   return ((b / nb) * 8u + (w >> 3)) * ts + (b % nb) * 8u + (w & 7u);
 }
 
+// Thin accretion disk (rrt_set_disk; rrt_device.h disk_cross): the annulus
+// r_in2 <= x^2 + y^2 - a^2 <= r_out2 of the Kerr local frame's plane z = 0, lengths in scene units.
+struct DDisk {
+  double r_in2, r_out2;   // (r_in M)^2, (r_out M)^2
+  double r_in;            // r_in M
+  double sqrt_m, k;       // sqrt(M), k = a sqrt(M)
+  float emission[3];
+  uint32_t on;            // 0: no disk (every build but the disk builds ignores the struct)
+  uint32_t no_redshift;   // RRT_DISK_NO_REDSHIFT: g = 1
+  uint32_t lensed;        // V_KERR_DISK: 1 = the lensed sky's rule, 0 = the reference's
+};
+
 #define RRT_MAX_QUEUES 8
 #define RRT_QUEUE_STRIDE 16  // counters 64 B apart
 
@@ -301,6 +313,7 @@ struct KParams {
   uint32_t cont_ticks;    // a heavy block stops waiting after this long without work (wall clock)
   uint32_t cont_waiters;  // heavy blocks blockIdx < cont_waiters wait for continuations; the others
                           // leave once the heavy list is done (their slots go back to the batch kernel)
+  DDisk disk;             // the accretion disk (last: every earlier field keeps its offset)
 #if RRT_PROFILE
   // diagnostic build: per-wave progress records in host-coherent memory (RRT_WATCHDOG_MS), read by
   // the host while the kernels run: [wave][4] = {iteration, state, pixel, marker}; batch waves

@@ -17,7 +17,18 @@ namespace rrt {
 template <bool DEEP, bool COUNT, int LEAN, int W = 0, class LV = LevelsPriv>
 __device__ __forceinline__ spec est_radiance(const KParams& kp, Rng& g, v3 o, v3 d, Counters& cn, LV lv = LV()) {  // :103-123
   Isect is;
-  if (is_sky(LEAN)) {  // lensed sky: the map along an escaping ray's exit direction; the hole's shadow is black
+  if (LEAN == V_KERR_DISK) {
+    // the disk build: a camera ray that reaches the disk returns its radiance; a miss takes the sky
+    // rule in force -- the lensed sky's (the far march runs) or the reference's (it does not)
+    ExitRec xr = {V(0.0, 0.0, 0.0), false};
+    DiskRec dk = {S(0, 0, 0), false};
+    if (!trace<false, COUNT, DEEP, LEAN>(kp, o, d, &is, cn, kp.disk.lensed ? &xr : nullptr, &dk)) {
+      if (!kp.env.w) return S(0, 0, 0);
+      if (!kp.disk.lensed) return env_dir(kp.env, d);
+      return xr.escaped ? env_dir(kp.env, xr.e) : S(0, 0, 0);
+    }
+    if (dk.hit) return dk.rgb;
+  } else if (is_sky(LEAN)) {  // lensed sky: the map along an escaping ray's exit direction; the hole's shadow is black
     ExitRec xr = {V(0.0, 0.0, 0.0), false};
     if (!trace<false, COUNT, DEEP, LEAN>(kp, o, d, &is, cn, &xr))
       return (xr.escaped && kp.env.w) ? env_dir(kp.env, xr.e) : S(0, 0, 0);
@@ -225,6 +236,8 @@ hipError_t rrt_launch_render(const KParams& kp, const KParams* d_kp, int deep, i
     RRT_LAUNCH(true, false, rrt::V_SKY, 2);
   } else if (lean == rrt::V_KERR_SKY) {
     RRT_LAUNCH(true, false, rrt::V_KERR_SKY, 2);
+  } else if (lean == rrt::V_KERR_DISK) {  // the accretion disk: one bounce-capable build, either sky rule; as V_KERR_SKY
+    RRT_LAUNCH(true, false, rrt::V_KERR_DISK, 2);
   } else if (lean == rrt::V_SW) {  // the reference's switches as run-time flags: one bounce-capable build
     if (count) RRT_LAUNCH(true, true, rrt::V_SW, 1); else RRT_LAUNCH(true, false, rrt::V_SW, 1);
   } else if (lean == rrt::V_KERR) {  // the Kerr builds (general integrator)

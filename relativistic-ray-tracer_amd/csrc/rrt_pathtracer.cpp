@@ -227,6 +227,11 @@ void PathTracer::set_lensed_sky(bool on) {
   apply_spacetime();
 }
 
+void PathTracer::set_disk(const rrt_disk_desc* disk) {
+  for (rrt_ctx* c : ctxs_)
+    if (rrt_set_disk(c, disk) != RRT_OK) err_ = rrt_last_error(c);
+}
+
 rrt_render_params PathTracer::params() const {
   rrt_render_params p;
   rrt_render_params_default(&p);

@@ -218,6 +218,62 @@ __global__ __launch_bounds__(256) void rrt_trace_exit_wave_kernel(const KParams*
   if (lane == 0) store_hit(a, i, RRT_RAY_MISS, (uint32_t)steps, false, is, qr);
 }
 
+// ------------------------------------------------------------------ accretion disk (rrt_set_disk)
+// Builds of their own again: the Kerr lane-per-ray kernel whose march tests the disk,
+// with (EXIT) and without the exit-mode far march.  A ray that ended on the disk: RRT_RAY_DISK, the
+// record a closest hit's (hit_p, n = +-ez g, w_out, t) with prim = bsdf = -1; any-hit: status and steps.
+template <bool EXIT, bool ANY, bool CAM>
+__global__ __launch_bounds__(256) void rrt_trace_disk_lane_kernel(const KParams* __restrict__ kpp, const TraceArgs a) {
+  using namespace rrt;
+  const KParams& kp = *kpp;
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= a.n) return;
+  v3 o, d;
+  load_ray<CAM>(kp, a, i, o, d);
+  Isect is;
+  QRec qr = {-1, 0.0, 0u, false};
+  ExitRec xr = {V(0.0, 0.0, 0.0), false};
+  DiskRec dk = {S(0, 0, 0), false};
+  Counters cn = {};
+  const bool hit = kerr_march<ANY, false, EXIT, true>(kp, o, d, &is, cn, &qr, &xr, &dk);
+  if (hit && dk.hit) {
+    double2* h = reinterpret_cast<double2*>(a.hits) + 6 * (size_t)i;
+    const double2 z = make_double2(0.0, 0.0);
+    if (ANY) {
+      h[0] = z; h[1] = z; h[2] = z; h[3] = z; h[4] = z;
+    } else {
+      h[0] = make_double2(is.hit_p.x, is.hit_p.y);
+      h[1] = make_double2(is.hit_p.z, is.n.x);
+      h[2] = make_double2(is.n.y, is.n.z);
+      h[3] = make_double2(is.w_out.x, is.w_out.y);
+      h[4] = make_double2(is.w_out.z, qr.t);
+    }
+    uint4 tail;
+    tail.x = RRT_RAY_DISK; tail.y = 0xffffffffu; tail.z = 0xffffffffu; tail.w = qr.steps;
+    *reinterpret_cast<uint4*>(h + 5) = tail;
+  } else if (hit || qr.captured || !EXIT) {
+    store_hit(a, i, hit ? RRT_RAY_HIT : qr.captured ? RRT_RAY_CAPTURED : RRT_RAY_MISS, qr.steps, hit && !ANY, is, qr);
+  } else {
+    store_exit(a, i, qr.steps, xr);
+  }
+}
+
+// the disk kernels' launch: Kerr, lane per ray
+hipError_t rrt_launch_trace_disk(const KParams* d_kp, const TraceArgs& a, int any, int exit, hipStream_t stream) {
+  const bool cam = a.rays == nullptr;
+  const uint32_t grid = (a.n - 1u) / 256u + 1u;  // n > 0
+#define RRT_GO_D(X, A, C) hipLaunchKernelGGL((rrt_trace_disk_lane_kernel<X, A, C>), dim3(grid), dim3(256), 0, stream, d_kp, a)
+#define RRT_PICK_D(X)                                                       \
+  do {                                                                      \
+    if (any) { if (cam) RRT_GO_D(X, true, true); else RRT_GO_D(X, true, false); } \
+    else     { if (cam) RRT_GO_D(X, false, true); else RRT_GO_D(X, false, false); } \
+  } while (0)
+  if (exit) RRT_PICK_D(true); else RRT_PICK_D(false);
+#undef RRT_PICK_D
+#undef RRT_GO_D
+  return hipGetLastError();
+}
+
 // ------------------------------------------------------------------ launch shim (C++ linkage)
 // mode: RRT_TRACE_*; AUTO takes wave-per-ray when every ray can hold a resident wave of its own at
 // once -- n <= CUs x the wave kernel's resident waves per CU -- since below that count lane-per-ray

@@ -86,6 +86,14 @@ class SpacetimeDesc(C.Structure):
                 ("delta_theta", C.c_double), ("spin", C.c_double), ("axis", C.c_double * 3)]
 
 
+RRT_DISK_NO_REDSHIFT = 1  # rrt_disk_desc.flags
+
+
+class DiskDesc(C.Structure):  # rrt_disk_desc
+    _fields_ = [("r_in", C.c_double), ("r_out", C.c_double), ("emission", C.c_float * 3), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+
 class RenderParams(C.Structure):
     _fields_ = [("ns_aa", C.c_uint32), ("max_ray_depth", C.c_uint32), ("ns_area_light", C.c_uint32),
                 ("samples_per_batch", C.c_uint32), ("max_tolerance", C.c_float),
@@ -104,6 +112,7 @@ class Stats(C.Structure):
 
 # ray queries (include/rrt.h "ray queries")
 RRT_RAY_MISS, RRT_RAY_HIT, RRT_RAY_CAPTURED, RRT_RAY_ESCAPED = 0, 1, 2, 3
+RRT_RAY_DISK = 4  # with a disk set (set_disk) only
 RRT_TRACE_ANY_HIT, RRT_TRACE_EXIT = 1, 4  # (bit 1 is unassigned)
 RRT_TRACE_AUTO, RRT_TRACE_LANE_PER_RAY, RRT_TRACE_WAVE_PER_RAY = 0, 1, 2
 TRACE_MODES = {"auto": RRT_TRACE_AUTO, "lane": RRT_TRACE_LANE_PER_RAY, "wave": RRT_TRACE_WAVE_PER_RAY}
@@ -134,7 +143,8 @@ EXPORTS = ["rrt_abi_version", "rrt_create", "rrt_destroy", "rrt_last_error", "rr
            "rrt_exr_load", "rrt_exr_free", "rrt_exr_save", "rrt_kerr_frame", "rrt_get_big_masks",
            "rrt_get_occluders", "rrt_group_create", "rrt_group_render", "rrt_group_destroy", "rrt_libm_eval",
            "rrt_set_proof_audit", "rrt_get_proof_audit", "rrt_get_search_tree4", "rrt_trace_rays",
-           "rrt_trace_rays_device", "rrt_trace_camera", "rrt_trace_camera_device", "rrt_env_eval"]
+           "rrt_trace_rays_device", "rrt_trace_camera", "rrt_trace_camera_device", "rrt_env_eval", "rrt_set_disk",
+           "rrt_get_disk"]
 AUDIT_KINDS = ("camera", "shadow", "pixel", "strip", "kerr", "zero")  # include/rrt.h RRT_AUDIT_*
 
 _lib = None
@@ -186,6 +196,9 @@ def lib():
         L.rrt_libm_eval.argtypes = [vp, C.c_int, vp, vp, vp, C.c_uint64]
         if hasattr(L, "rrt_env_eval"):  # absent from older builds loaded through RRT_LIB
             L.rrt_env_eval.argtypes = [vp, vp, C.c_uint64, vp]
+        if hasattr(L, "rrt_set_disk"):  # absent from older builds loaded through RRT_LIB
+            L.rrt_set_disk.argtypes = [vp, C.POINTER(DiskDesc)]
+            L.rrt_get_disk.argtypes = [vp, C.POINTER(DiskDesc)]
         if hasattr(L, "rrt_set_proof_audit"):  # absent from older builds loaded through RRT_LIB
             L.rrt_set_proof_audit.argtypes = [vp, C.c_int]
             L.rrt_get_proof_audit.argtypes = [vp, vp]
@@ -446,6 +459,29 @@ class Renderer:
 
     LIBM_FN = {"sin": 0, "cos": 1, "acos": 2, "atan2": 3, "sinf": 4, "cosf": 5, "exp": 6, "log": 7, "erf": 8,
                "atan": 9, "tan": 10}
+
+    def set_disk(self, r_in=0.0, r_out=None, emission=(1.0, 1.0, 1.0), redshift=True):
+        """The thin accretion disk of a Kerr hole (rrt_set_disk): the annulus r_in..r_out
+        (in M; r_in=0: the prograde ISCO of the spin in force) of the equatorial plane, radiance
+        emission x (r_in / r)^3 x g^4; redshift=False: g = 1.  set_disk(None) removes it."""
+        if r_in is None:
+            self._chk(lib().rrt_set_disk(self.h, None))
+            return
+        if r_out is None:
+            raise ValueError("set_disk needs r_out")
+        d = DiskDesc()
+        d.r_in, d.r_out = r_in, r_out
+        d.emission[0], d.emission[1], d.emission[2] = emission
+        d.flags = 0 if redshift else RRT_DISK_NO_REDSHIFT
+        self._chk(lib().rrt_set_disk(self.h, C.byref(d)))
+
+    def get_disk(self):
+        """The disk in force as a dict (r_in resolved: 0 -> the ISCO of a Kerr spacetime), or None."""
+        d = DiskDesc()
+        if not lib().rrt_get_disk(self.h, C.byref(d)):
+            return None
+        return {"r_in": d.r_in, "r_out": d.r_out, "emission": tuple(d.emission),
+                "redshift": not (d.flags & RRT_DISK_NO_REDSHIFT)}
 
     def libm_eval(self, fn, a, b=None):
         """The device's restated host-libm function `fn` (rrt_glibm.h) on float64 arrays a (, b)."""
