@@ -162,15 +162,30 @@ int rrt_set_spacetime(rrt_ctx* ctx, const rrt_spacetime_desc* st);
  * 0), for an r_in below the prograde ISCO of the current spin, and, rendering, with
  * RRT_RENDER_WAVEFRONT, RRT_RENDER_DEEP_SAMPLE, RRT_RENDER_COUNTERS or the reference's switch
  * flags.  The members of a group share the disk as they share the spacetime.  Without a disk every
+ * output is what it was.
+ * RRT_DISK_BLACKBODY moves the spectrum instead of one brightness: the gas at r is a
+ * blackbody at T(r) = temperature x (r_in / r)^(3/4) (RRT_DISK_PROFILE_POWER: T^4 follows the plain
+ * disk's flux) or temperature x (c^3 (1 - sqrt c) x 823543 / 46656)^(1/4), c = r_in / r
+ * (RRT_DISK_PROFILE_ZERO_TORQUE: `temperature` is the peak, reached at r = 49/36 r_in; the inner edge
+ * is black), seen at redshift g as a blackbody at g T (the g^4 is inside).  Per channel, at 610, 550
+ * and 465 nm, the pixel is emission x the Planck ratio B(g T) / B(temperature): `emission` is the
+ * RGB radiance of gas at `temperature` seen at g = 1 (rrt_blackbody_tint gives the physical one).
+ * Rendered by a build of its own; the ray-query records are the plain disk's.  Without the flag every
  * output is what it was. */
-enum { RRT_DISK_NO_REDSHIFT = 1u << 0 };  /* g = 1: the bare (r_in / r)^3 profile */
+enum { RRT_DISK_NO_REDSHIFT = 1u << 0,   /* g = 1: the bare profile */
+       RRT_DISK_BLACKBODY = 1u << 2 };   /* bit 1 is unassigned and rejected */
+enum { RRT_DISK_PROFILE_POWER = 0, RRT_DISK_PROFILE_ZERO_TORQUE = 1 };
 typedef struct {
   double r_in, r_out;         /* in M; r_in == 0: the prograde ISCO of the spin in force at launch */
-  float emission[3];          /* radiance at r = r_in for g = 1 */
+  float emission[3];          /* radiance at r = r_in for g = 1; blackbody: of gas at `temperature` for g = 1 */
   uint32_t flags;             /* RRT_DISK_* */
-  uint32_t reserved[4];
-} rrt_disk_desc;
-/* NULL removes the disk.  RRT_E_INVALID: a non-finite or negative value, r_out <= r_in, unknown flags. */
+  float temperature;          /* Kelvin, in [1000, 1e6]; read only with RRT_DISK_BLACKBODY (else stored as 0) */
+  uint32_t profile;           /* RRT_DISK_PROFILE_*; read only with RRT_DISK_BLACKBODY (else stored as 0) */
+  uint32_t reserved[2];
+} rrt_disk_desc;                /* 48 bytes */
+/* NULL removes the disk.  RRT_E_INVALID: a non-finite or negative value, r_out <= r_in, unknown flags;
+ * with RRT_DISK_BLACKBODY a temperature that is not finite or outside [1000, 1e6] K, an unknown profile.
+ * A rejected descriptor leaves the disk in force. */
 int rrt_set_disk(rrt_ctx* ctx, const rrt_disk_desc* disk);
 /* 1 and the disk in force (r_in resolved against the current spacetime: 0 -> the ISCO radius in M
  * if the spacetime is Kerr), or 0 without a disk; works on a host-only context. */
@@ -469,6 +484,18 @@ int rrt_libm_eval(rrt_ctx* ctx, int fn, const double* a, const double* b, double
  * along a direction, normalised by the lookup) on n host directions: dirs [n][3] -> rgb [n][3].
  * RRT_E_INVALID without an environment map, RRT_E_NO_DEVICE on a host-only context. */
 int rrt_env_eval(rrt_ctx* ctx, const double* dirs, uint64_t n, float* rgb);
+/* The device's colour rule of the disk in force, plain or blackbody (rrt_device.h disk_rgb, DESIGN.md
+ * §12 / §13), on n host pairs: the Boyer-Lindquist radius r_m[i] in M (x M: one multiplication) and
+ * the redshift g[i], taken as given (ignored with RRT_DISK_NO_REDSHIFT) -> rgb [n][3].  n == 0: RRT_OK
+ * without a launch.  Without a disk, or with one invalid for the current spacetime, the errors of a
+ * render launch; RRT_E_NO_DEVICE on a host-only context. */
+int rrt_disk_eval(rrt_ctx* ctx, const double* r_m, const double* g, uint64_t n, float* rgb);
+/* Host only: the three-wavelength Planck colour of a blackbody at T Kelvin normalised to G = 1,
+ * rgb[c] = (float)(W_c (exp(K_G / T) - 1) / (exp(K_c / T) - 1)), W_c = (550 / lambda_c)^5,
+ * K_c = 14387768.77 nm K / lambda_c, lambda = 610, 550, 465 nm -- the physical `emission` of a
+ * blackbody disk of that temperature (3000 K orange, 6500 K near white, 20000 K blue).
+ * RRT_E_INVALID outside [1000, 1e6] K. */
+int rrt_blackbody_tint(double T, float rgb[3]);
 /* Run-time proof audit.  The renderer skips marches whose results its proofs
  * determine (camera-ray miss, shadow-ray occlusion, pixel and strip miss, Kerr occlusion); their
  * margins are validated by sweeps.  With the audit set, every counting launch that runs the proofs

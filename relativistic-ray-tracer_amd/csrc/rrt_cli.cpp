@@ -9,8 +9,9 @@
 // axis, default +y; build-defined) and --lensed-sky (escaping rays see the environment
 // map along their exit direction) and --disk R_IN R_OUT [--disk-emission R G B]
 // [--disk-no-redshift] (a thin accretion disk, radii in M, R_IN 0 = the ISCO; needs --kerr; DESIGN.md
-// §12).  The interactive viewer is out of scope: -f is
-// required.  Exit codes follow main.cpp (usage -> 1).
+// §12) [--disk-temp KELVIN] [--disk-profile power|zero-torque] (the blackbody disk, DESIGN.md §13;
+// without --disk-emission the emission is rrt_blackbody_tint of KELVIN).  The interactive viewer is
+// out of scope: -f is required.  Exit codes follow main.cpp (usage -> 1).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -42,6 +43,8 @@ static void usage(const char* binary) {
   std::printf("  --lensed-sky     Look the environment map up along the bent ray; the hole's shadow is black\n");
   std::printf("  --disk <R_IN> <R_OUT>  Thin accretion disk, radii in M (R_IN 0: the ISCO); needs --kerr\n");
   std::printf("  --disk-emission <R> <G> <B>  Disk radiance at R_IN (default 1 1 1)   --disk-no-redshift  g = 1\n");
+  std::printf("  --disk-temp <KELVIN>  Blackbody disk: temperature in [1000, 1e6] K; the emission defaults to its Planck colour\n");
+  std::printf("  --disk-profile <power|zero-torque>  Blackbody disk: T ~ r^-3/4, or the zero-torque profile peaking at KELVIN\n");
   std::printf("  -h               Print this help message\n");
 }
 
@@ -58,7 +61,7 @@ int main(int argc, char** argv) {
   unsigned long long seed = 0;
   int device = 0;
   std::vector<int> devices;  // --devices: several GPUs (rrt_group)
-  bool to_file = false, lensed_sky = false, has_disk = false;
+  bool to_file = false, lensed_sky = false, has_disk = false, has_emission = false, has_temp = false, has_profile = false;
   rrt_disk_desc disk;
   std::memset(&disk, 0, sizeof(disk));
   disk.emission[0] = disk.emission[1] = disk.emission[2] = 1.0f;
@@ -113,6 +116,20 @@ int main(int argc, char** argv) {
     else if (a == "--disk-emission") {
       need(i, 3);
       for (int k = 0; k < 3; ++k) disk.emission[k] = (float)std::atof(argv[++i]);
+      has_emission = true;
+    }
+    else if (a == "--disk-temp") {
+      need(i, 1);
+      disk.temperature = (float)std::atof(argv[++i]);
+      has_temp = true;
+    }
+    else if (a == "--disk-profile") {
+      need(i, 1);
+      const std::string v = argv[++i];
+      if (v == "power") disk.profile = RRT_DISK_PROFILE_POWER;
+      else if (v == "zero-torque") disk.profile = RRT_DISK_PROFILE_ZERO_TORQUE;
+      else { usage(argv[0]); return 1; }
+      has_profile = true;
     }
     else if (a == "--disk-no-redshift") { disk.flags |= RRT_DISK_NO_REDSHIFT; }
     else if (a == "--kerr") {
@@ -129,6 +146,21 @@ int main(int argc, char** argv) {
     else { usage(argv[0]); return 1; }
   }
   if (scene_path.empty()) { usage(argv[0]); return 1; }
+  if ((has_temp || has_profile) && !has_disk) {
+    std::fprintf(stderr, "[rrt_render] --disk-temp and --disk-profile need --disk R_IN R_OUT\n");
+    return 1;
+  }
+  if (has_profile && !has_temp) {
+    std::fprintf(stderr, "[rrt_render] --disk-profile needs --disk-temp KELVIN\n");
+    return 1;
+  }
+  if (has_temp) {  // the blackbody disk: its physical colour unless the caller gave one
+    disk.flags |= RRT_DISK_BLACKBODY;
+    if (!has_emission && rrt_blackbody_tint((double)disk.temperature, disk.emission) != RRT_OK) {
+      std::fprintf(stderr, "[rrt_render] --disk-temp must lie in [1000, 1e6] K\n");
+      return 1;
+    }
+  }
   if (!to_file) {
     std::fprintf(stderr, "[rrt_render] the interactive viewer is not part of this build: pass -f <file.png>\n");
     return 1;

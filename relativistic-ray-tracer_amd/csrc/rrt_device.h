@@ -851,11 +851,15 @@ constexpr int V_KERR_SKY = 6;
 // the exit-mode march and takes the lensed sky's rule or the reference's at run time (kp.disk.lensed).
 // Per-pixel-loop kernel only; no proofs.
 constexpr int V_KERR_DISK = 7;
+// V_KERR_DISK_BB: V_KERR_DISK with the blackbody colour rule (RRT_DISK_BLACKBODY) in
+// place of the plain one: a build of its own, so that V_KERR_DISK keeps its registers and scratch.
+constexpr int V_KERR_DISK_BB = 8;
 __host__ __device__ constexpr bool is_lean(int v) { return v == 1 || v == 2; }
 __host__ __device__ constexpr bool is_sky(int v) { return v == V_SKY || v == V_KERR_SKY; }
-__host__ __device__ constexpr bool is_kerr_build(int v) { return v == V_KERR || v == V_KERR_SKY || v == V_KERR_DISK; }
+__host__ __device__ constexpr bool is_disk(int v) { return v == V_KERR_DISK || v == V_KERR_DISK_BB; }
+__host__ __device__ constexpr bool is_kerr_build(int v) { return v == V_KERR || v == V_KERR_SKY || is_disk(v); }
 __host__ __device__ constexpr int general_of(int v) {  // non-LEAN build
-  return v == V_KERR || v == V_SW || is_sky(v) || v == V_KERR_DISK ? v : 0;
+  return v == V_KERR || v == V_SW || is_sky(v) || is_disk(v) ? v : 0;
 }
 
 // ------------------------------------------------------------------ Kerr (build-defined)
@@ -1018,7 +1022,7 @@ __device__ __forceinline__ void audit_note(const KParams& kp, int k, bool violat
   if (violated) atomicAdd(kp.audit + 2 * k + 1, 1ull);
 }
 __device__ __forceinline__ bool kerr_occluded_proof(const KParams& kp, v3 o, v3 d);
-template <bool ANY, bool COUNT, bool EXIT = false, bool DISK = false>
+template <bool ANY, bool COUNT, bool EXIT = false, bool DISK = false, bool BB = false>
 __device__ __forceinline__ bool kerr_march(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn, QRec* qr = nullptr,
                                            ExitRec* xr = nullptr, DiskRec* dk = nullptr);
 template <bool ANY, bool COUNT>
@@ -1077,8 +1081,11 @@ __device__ __forceinline__ bool disk_cross(const DHole& h, const DDisk& dd, v3 q
 // moves on the prograde circular geodesic of radius r: Omega = sqrt(M) / (r^1.5 + k), k = a sqrt(M),
 // u^t = (1 + k / r^1.5) / sqrt(1 - 3M / r + 2k / r^1.5).  The march's photon has E = 1 (p_t = -1) and
 // L_z = x p_y - y p_x, so g = E_observed / E_emitted = 1 / (u^t (1 - Omega L_z)), the observer's own
-// constant factor left out; a g that is not finite and positive counts as 0.  The radiance is
-// emission x (r_in / r)^3 x g^4 (bolometric).  g out.
+// constant factor left out; a g that is not finite and positive counts as 0.  The colour is disk_rgb's.
+// g out.
+template <bool BB>
+__device__ __forceinline__ spec disk_rgb(const DDisk& dd, double r, double g);
+template <bool BB = false>
 __device__ __forceinline__ spec disk_radiance(const DHole& h, const DDisk& dd, double x, double y, double lz, double& g_out) {
   const double r = xsqrt((x * x + y * y) - h.a2);
   double g = 1.0;
@@ -1090,20 +1097,50 @@ __device__ __forceinline__ spec disk_radiance(const DHole& h, const DDisk& dd, d
     g = xdiv(1.0, ut * (1.0 - om * lz));
     if (!(g > 0.0 && isfinite(g))) g = 0.0;
   }
-  const double c = xdiv(dd.r_in, r);
-  double w = (c * c) * c;
-  if (!dd.no_redshift) {
-    const double g2 = g * g;
-    w = w * (g2 * g2);
-  }
   g_out = g;
-  return S(dd.emission[0] * (float)w, dd.emission[1] * (float)w, dd.emission[2] * (float)w);
+  return disk_rgb<BB>(dd, r, g);
+}
+// The colour of the disk at radius r (scene units) seen at redshift g (ignored, as 1, with
+// dd.no_redshift).  Plain: emission x (r_in / r)^3 x g^4 (bolometric).  BB (§13,
+// RRT_DISK_BLACKBODY): the gas at r is a blackbody at T = temperature x q^(1/4), q = c^3 (POWER) or
+// c^3 (1 - sqrt c) F_NORM (ZERO_TORQUE, 1 at its peak c = 36 / 49), c = r_in / r; seen at redshift g it
+// is a blackbody at g T (I_nu / nu^3 is invariant: the g^4 is inside), and per channel the Planck
+// ratio (exp(K_c / temperature) - 1) / (exp(K_c / (g T)) - 1) scales emission, the colour of gas at
+// `temperature` seen at g = 1.  Anything not finite and positive on the way: black.
+template <bool BB>
+__device__ __forceinline__ spec disk_rgb(const DDisk& dd, double r, double g) {
+  const double c = xdiv(dd.r_in, r);
+  const double c3 = (c * c) * c;
+  if (!BB) {
+    double w = c3;
+    if (!dd.no_redshift) {
+      const double g2 = g * g;
+      w = w * (g2 * g2);
+    }
+    return S(dd.emission[0] * (float)w, dd.emission[1] * (float)w, dd.emission[2] * (float)w);
+  }
+  double q = c3;
+  if (dd.profile == RRT_DISK_PROFILE_ZERO_TORQUE) q = (c3 * (1.0 - xsqrt(c))) * RRT_BB_F_NORM;
+  if (!(q > 0.0)) return S(0, 0, 0);
+  const double t = dd.temperature * xsqrt(xsqrt(q));
+  const double t_obs = (dd.no_redshift ? 1.0 : g) * t;
+  if (!(t_obs > 0.0 && isfinite(t_obs))) return S(0, 0, 0);
+  float f[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double den = rrt_glibm_exp(xdiv(dd.bb_k[k], t_obs)) - 1.0;
+    double ratio = xdiv(dd.bb_n[k], den);
+    if (!isfinite(ratio)) ratio = 0.0;
+    f[k] = dd.emission[k] * (float)ratio;
+  }
+  return S(f[0], f[1], f[2]);
 }
 // the march of query_kerr (no proof).  EXIT: an escaping photon goes on to its exit direction (*xr).
 // DISK: with kp.disk.on every step is tested against the accretion disk next to its chord's segment
 // query: a capture wins; else the chord's closest primitive hit wins iff its
 // t <= t_disk = s max_t, else the disk (*dk; the Isect and qr->t as for a hit, bsdf and slot -1).
-template <bool ANY, bool COUNT, bool EXIT, bool DISK>
+// BB: dk->rgb is the blackbody colour.
+template <bool ANY, bool COUNT, bool EXIT, bool DISK, bool BB>
 __device__ __forceinline__ bool kerr_march(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn, QRec* qr, ExitRec* xr,
                                            DiskRec* dk) {
   const DHole& h = kp.hole;
@@ -1167,7 +1204,7 @@ __device__ __forceinline__ bool kerr_march(const KParams& kp, v3 o, v3 d, Isect*
         if (prim && !(cross && q2->t > t_disk)) return true;
         if (cross) {
           double g;
-          const spec rgb = disk_radiance(h, kp.disk, x, y, lz, g);
+          const spec rgb = disk_radiance<BB>(h, kp.disk, x, y, lz, g);
           if (dk) { dk->hit = true; dk->rgb = rgb; }
           const double gs = above ? g : -g;
           is->hit_p = a + vmul(sd, t_disk);
@@ -1427,11 +1464,12 @@ __device__ __forceinline__ bool shadow_occluded_proof(const KParams& kp, v3 o, v
 // EXIT: the exit-mode march (no proofs): the Schwarzschild march stops at the escape
 // row -- that row's capture test and walk, and every later row, are not run -- and *xr (if given)
 // says whether and where the ray escaped; Kerr: kerr_march's far march.
-// DISK (Kerr exit-mode builds): the march tests the accretion disk too (kerr_march; *dk)
-template <bool ANY, bool COUNT, bool KERR = false, bool W4 = true, bool EXIT = false, bool DISK = false>
+// DISK (Kerr exit-mode builds): the march tests the accretion disk too (kerr_march; *dk); BB: its
+// colour is the blackbody rule's
+template <bool ANY, bool COUNT, bool KERR = false, bool W4 = true, bool EXIT = false, bool DISK = false, bool BB = false>
 RRT_QUERY_ATTR bool query(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn, bool any_rt = false,
                           QRec* qr = nullptr, ExitRec* xr = nullptr, DiskRec* dk = nullptr) {
-  if (KERR && EXIT) return kerr_march<ANY, COUNT, true, DISK>(kp, o, d, is, cn, qr, xr, dk);
+  if (KERR && EXIT) return kerr_march<ANY, COUNT, true, DISK, BB>(kp, o, d, is, cn, qr, xr, dk);
   if (KERR) return qr ? kerr_march<ANY, COUNT>(kp, o, d, is, cn, qr) : query_kerr<ANY, COUNT>(kp, o, d, is, cn);
   if (qr) qr->steps = (uint32_t)kp.hole.steps;  // all marched, unless a segment below ends the march
   if (COUNT && !kp.count_exec && !(kp.diag & 2)) cn.query++;

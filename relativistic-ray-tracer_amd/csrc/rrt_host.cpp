@@ -38,6 +38,8 @@ hipError_t rrt_launch_path(const KParams* d_kp, int waves, uint32_t grid, hipStr
 hipError_t rrt_launch_env(const DEnv& env, uint64_t n, const double* dirs, float* rgb, hipStream_t stream);
 hipError_t rrt_launch_trace(const KParams* d_kp, const TraceArgs& a, int kerr, int any, int exit, int mode, int n_cu, int* mode_out,
                             hipStream_t stream);
+hipError_t rrt_launch_disk(const DDisk& disk, double m, uint64_t n, const double* r_m, const double* g, float* rgb,
+                           hipStream_t stream);
 hipError_t rrt_launch_trace_disk(const KParams* d_kp, const TraceArgs& a, int any, int exit, hipStream_t stream);
 hipError_t rrt_launch_unpack(const uint32_t* tiles, uint32_t n_tiles, uint32_t ts, uint32_t fw, uint32_t fh,
                              const float* rgb_p, const int32_t* cnt_p, float* rgb, int32_t* cnt, hipStream_t stream);
@@ -1285,8 +1287,16 @@ extern "C" int rrt_set_disk(rrt_ctx* c, const rrt_disk_desc* d) {
     if (!(std::isfinite(d->emission[k]) && d->emission[k] >= 0.0f))
       return fail(c, RRT_E_INVALID, "disk emission must be finite and >= 0");
   if (!(d->r_out > d->r_in)) return fail(c, RRT_E_INVALID, "disk needs r_out > r_in");
-  if (d->flags & ~(uint32_t)RRT_DISK_NO_REDSHIFT) return fail(c, RRT_E_INVALID, "unknown rrt_disk_desc flags");
+  if (d->flags & ~(uint32_t)(RRT_DISK_NO_REDSHIFT | RRT_DISK_BLACKBODY))
+    return fail(c, RRT_E_INVALID, "unknown rrt_disk_desc flags");
+  if (d->flags & RRT_DISK_BLACKBODY) {  // DESIGN.md §13; the range keeps every intermediate of the rule finite
+    if (!(std::isfinite(d->temperature) && d->temperature >= (float)RRT_BB_T_MIN && d->temperature <= (float)RRT_BB_T_MAX))
+      return fail(c, RRT_E_INVALID, "a blackbody disk's temperature must lie in [1000, 1e6] K");
+    if (d->profile != RRT_DISK_PROFILE_POWER && d->profile != RRT_DISK_PROFILE_ZERO_TORQUE)
+      return fail(c, RRT_E_INVALID, "unknown rrt_disk_desc profile");
+  }
   c->disk = *d;
+  if (!(d->flags & RRT_DISK_BLACKBODY)) { c->disk.temperature = 0.0f; c->disk.profile = 0u; }  // as reserved
   for (uint32_t& r : c->disk.reserved) r = 0u;
   c->has_disk = true;
   return RRT_OK;
@@ -1325,6 +1335,13 @@ static int fill_disk_params(rrt_ctx* c, KParams& kp) {
   d.on = 1u;
   d.no_redshift = (c->disk.flags & RRT_DISK_NO_REDSHIFT) ? 1u : 0u;
   d.lensed = c->lensed_sky ? 1u : 0u;
+  d.blackbody = 0u;
+  if (c->disk.flags & RRT_DISK_BLACKBODY) {  // the build V_KERR_DISK_BB
+    d.blackbody = 1u;
+    d.profile = c->disk.profile;
+    d.temperature = (double)c->disk.temperature;
+    rrt_bb_constants(d.temperature, d.bb_k, d.bb_n);
+  }
   const double e2 = d.r_out2 + h.a2;  // |q|^2 on the plane at r_out
   if (e2 > kp.hole.r_esc2) kp.hole.r_esc2 = e2;
   return RRT_OK;
@@ -1682,7 +1699,7 @@ static int launch(rrt_ctx* c, const rrt_render_params* p, const uint32_t* tiles,
     return fail(c, RRT_E_INVALID, "RRT_RENDER_WAVEFRONT (the path pool kernel) renders max_ray_depth >= 2 "
                                   "Schwarzschild frames without counters or switches, n_lights x ns_area_light < 2048");
   const bool pixel_loop = !path_pool && ((deep && !deep_sample) || (p->flags & RRT_RENDER_PIXEL_LOOP) || sw || sky || disk);
-  const int lean = disk ? 7 /* V_KERR_DISK */
+  const int lean = disk ? (kp.disk.blackbody ? 8 /* V_KERR_DISK_BB */ : 7 /* V_KERR_DISK */)
                  : sky ? (kerr ? 6 /* V_KERR_SKY */ : 5 /* V_SKY */)
                  : kerr ? 3 /* V_KERR */
                  : sw ? 4 /* V_SW */
@@ -2187,6 +2204,32 @@ extern "C" int rrt_env_eval(rrt_ctx* c, const double* dirs, uint64_t n, float* r
   env.w = c->env_w; env.h = c->env_h;
   HIPCHK(c, rrt_launch_env(env, n, dd, dr, (hipStream_t)0));
   HIPCHK(c, hipMemcpy(rgb, dr, sizeof(float) * 3 * n, hipMemcpyDeviceToHost));
+  return RRT_OK;
+}
+
+extern "C" int rrt_disk_eval(rrt_ctx* c, const double* r_m, const double* g, uint64_t n, float* rgb) {
+  if (!c || (n && (!r_m || !g || !rgb))) return fail(c, RRT_E_INVALID, "bad argument");
+  if (!c->has_disk) return fail(c, RRT_E_INVALID, "no accretion disk (rrt_set_disk)");
+  KParams probe{};  // the disk's device constants as a launch fills them
+  probe.hole = c->hole;
+  if (int rc = fill_disk_params(c, probe)) return rc;
+  if (c->device < 0) return fail(c, RRT_E_NO_DEVICE, "no device");
+  if (n == 0) return RRT_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  double* dr = nullptr;
+  double* dg = nullptr;
+  float* dc = nullptr;
+  struct Free {
+    void** p[3];
+    ~Free() { for (void** q : p) if (*q) (void)hipFree(*q); }
+  } guard{{(void**)&dr, (void**)&dg, (void**)&dc}};
+  HIPCHK(c, hipMalloc(&dr, sizeof(double) * n));
+  HIPCHK(c, hipMalloc(&dg, sizeof(double) * n));
+  HIPCHK(c, hipMalloc(&dc, sizeof(float) * 3 * n));
+  HIPCHK(c, hipMemcpy(dr, r_m, sizeof(double) * n, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(dg, g, sizeof(double) * n, hipMemcpyHostToDevice));
+  HIPCHK(c, rrt_launch_disk(probe.disk, probe.hole.m, n, dr, dg, dc, (hipStream_t)0));
+  HIPCHK(c, hipMemcpy(rgb, dc, sizeof(float) * 3 * n, hipMemcpyDeviceToHost));
   return RRT_OK;
 }
 

@@ -11,13 +11,14 @@ namespace rrt {
 // `trace` = the geodesic-marched BVH query; DEEP (bounce) builds and depth <= 1 builds share it.
 // The lensed-sky builds (V_SKY, V_KERR_SKY) run the exit-mode march for every query; xr: where the
 // ray went if it hit nothing (they only).
-// The disk build (V_KERR_DISK) runs the exit-mode march with the disk test; its far
-// march runs only where xr is given (the lensed sky's rule in force).  dk: a hit that is the disk.
+// The disk builds (V_KERR_DISK; V_KERR_DISK_BB, §13: the blackbody colour) run the
+// exit-mode march with the disk test; its far march runs only where xr is given (the lensed sky's rule
+// in force).  dk: a hit that is the disk.
 template <bool ANY, bool COUNT, bool DEEP, int LEAN>
 __device__ __forceinline__ bool trace(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn, ExitRec* xr = nullptr,
                                       DiskRec* dk = nullptr) {
-  return query<ANY, COUNT, is_kerr_build(LEAN), is_lean(LEAN), is_sky(LEAN) || LEAN == V_KERR_DISK, LEAN == V_KERR_DISK>(
-      kp, o, d, is, cn, false, nullptr, xr, dk);
+  return query<ANY, COUNT, is_kerr_build(LEAN), is_lean(LEAN), is_sky(LEAN) || is_disk(LEAN), is_disk(LEAN),
+               LEAN == V_KERR_DISK_BB>(kp, o, d, is, cn, false, nullptr, xr, dk);
 }
 // the emission a ray picks up at its hit: the hit primitive's BSDF's, or the disk's radiance
 __device__ __forceinline__ spec hit_emission(const KParams& kp, const Isect& is, const DiskRec& dk) {
@@ -43,7 +44,7 @@ __device__ spec direct_importance(const KParams& kp, Rng& g, const Isect& is, Co
       const Frame f = coord_space(is.n);
       v3 w_in = to_local(f, wi_world);
       if (w_in.z < 0) continue;
-      if ((is_sky(LEAN) || (LEAN == V_KERR_DISK && kp.disk.lensed)) && l.type == 5u) {
+      if ((is_sky(LEAN) || (is_disk(LEAN) && kp.disk.lensed)) && l.type == 5u) {
         // lensed sky: the environment light's sample counts iff its shadow ray escapes, with the
         // map's radiance along the exit direction; wi, pdf, the BSDF term and the draws as they are
         ExitRec xr = {V(0.0, 0.0, 0.0), false};
@@ -70,7 +71,7 @@ __device__ spec direct_hemisphere(const KParams& kp, Rng& g, const Isect& is, Co
     v3 w_in = hemisphere_sample(g);
     v3 wi_world = to_world(f, w_in);
     Isect is2;
-    if (LEAN == V_KERR_DISK) {  // the emitter term takes the disk's radiance where the ray ends on the disk
+    if (is_disk(LEAN)) {  // the emitter term takes the disk's radiance where the ray ends on the disk
       DiskRec dk = {S(0, 0, 0), false};
       if (trace<false, COUNT, DEEP, LEAN>(kp, is.hit_p + smul(EPS_D, wi_world), wi_world, &is2, cn, nullptr, &dk))
         L = L + (hit_emission(kp, is2, dk) * bsdf_f(b, w_out, w_in)) * (float)w_in.z;
@@ -175,7 +176,7 @@ __device__ __forceinline__ spec at_least_one_bounce(const KParams& kp, Rng& g, I
       if (pdf == 0.0f) break;
       v3 wi_world = to_world(f, w_in);
       Isect is2;
-      if (LEAN == V_KERR_DISK) {  // a bounce ray that ends on the disk ends the path there
+      if (is_disk(LEAN)) {  // a bounce ray that ends on the disk ends the path there
         DiskRec dk = {S(0, 0, 0), false};
         if (trace<false, COUNT, true, LEAN>(kp, cur.hit_p + smul(EPS_D, wi_world), wi_world, &is2, cn, nullptr, &dk) &&
             k + 1 < LV::D) {

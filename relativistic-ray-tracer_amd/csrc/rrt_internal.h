@@ -3,6 +3,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "rrt_blackbody.h"
+
 #define RRT_MAX_LIGHTS 16
 #define RRT_MAX_BSDFS 64
 #define RRT_MAX_DEPTH 16
@@ -180,6 +182,13 @@ struct DDisk {
   uint32_t on;            // 0: no disk (every build but the disk builds ignores the struct)
   uint32_t no_redshift;   // RRT_DISK_NO_REDSHIFT: g = 1
   uint32_t lensed;        // V_KERR_DISK: 1 = the lensed sky's rule, 0 = the reference's
+  // the blackbody disk (RRT_DISK_BLACKBODY; rrt_device.h disk_rgb); behind the plain
+  // disk's fields, which keep their offsets
+  double temperature;     // Kelvin: the gas at r_in (POWER) or at the profile's peak (ZERO_TORQUE)
+  double bb_k[3];         // K_c = (hc / k in nm K) / lambda_c
+  double bb_n[3];         // N_c = exp(K_c / temperature) - 1 (rrt_glibm_exp on the host)
+  uint32_t blackbody;     // 1: RRT_DISK_BLACKBODY (rendered by V_KERR_DISK_BB)
+  uint32_t profile;       // RRT_DISK_PROFILE_*
 };
 
 #define RRT_MAX_QUEUES 8

@@ -17,7 +17,7 @@ namespace rrt {
 template <bool DEEP, bool COUNT, int LEAN, int W = 0, class LV = LevelsPriv>
 __device__ __forceinline__ spec est_radiance(const KParams& kp, Rng& g, v3 o, v3 d, Counters& cn, LV lv = LV()) {  // :103-123
   Isect is;
-  if (LEAN == V_KERR_DISK) {
+  if (is_disk(LEAN)) {
     // the disk build: a camera ray that reaches the disk returns its radiance; a miss takes the sky
     // rule in force -- the lensed sky's (the far march runs) or the reference's (it does not)
     ExitRec xr = {V(0.0, 0.0, 0.0), false};
@@ -220,6 +220,16 @@ __global__ void rrt_env_kernel(const DEnv env, uint64_t n, const double* dirs, f
     rgb[3 * k] = s.r; rgb[3 * k + 1] = s.g; rgb[3 * k + 2] = s.b;
   }
 }
+// The disk's colour as the march evaluates it (rrt_device.h disk_rgb, plain or blackbody) at n radii
+// r_m (Boyer-Lindquist r in M; x m: scene units) and redshifts g: rrt_disk_eval, the checker's handle
+// on radii and redshifts no camera ray reaches (tests/test_gpu_blackbody.py)
+__global__ void rrt_disk_kernel(const DDisk disk, double m, uint64_t n, const double* r_m, const double* g, float* rgb) {
+  for (uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; k < n; k += (uint64_t)gridDim.x * blockDim.x) {
+    const double r = r_m[k] * m;
+    const rrt::spec s = disk.blackbody ? rrt::disk_rgb<true>(disk, r, g[k]) : rrt::disk_rgb<false>(disk, r, g[k]);
+    rgb[3 * k] = s.r; rgb[3 * k + 1] = s.g; rgb[3 * k + 2] = s.b;
+  }
+}
 
 // ------------------------------------------------------------------ launch shims (C++ linkage)
 // Kernel selection: deep / counting variants are built once (1 wave per SIMD budget); the
@@ -238,6 +248,8 @@ hipError_t rrt_launch_render(const KParams& kp, const KParams* d_kp, int deep, i
     RRT_LAUNCH(true, false, rrt::V_KERR_SKY, 2);
   } else if (lean == rrt::V_KERR_DISK) {  // the accretion disk: one bounce-capable build, either sky rule; as V_KERR_SKY
     RRT_LAUNCH(true, false, rrt::V_KERR_DISK, 2);
+  } else if (lean == rrt::V_KERR_DISK_BB) {  // ... with the blackbody colour: a build of its own
+    RRT_LAUNCH(true, false, rrt::V_KERR_DISK_BB, 2);
   } else if (lean == rrt::V_SW) {  // the reference's switches as run-time flags: one bounce-capable build
     if (count) RRT_LAUNCH(true, true, rrt::V_SW, 1); else RRT_LAUNCH(true, false, rrt::V_SW, 1);
   } else if (lean == rrt::V_KERR) {  // the Kerr builds (general integrator)
@@ -301,6 +313,14 @@ hipError_t rrt_launch_env(const DEnv& env, uint64_t n, const double* dirs, float
   if (grid > 8192) grid = 8192;
   if (grid == 0) grid = 1;
   hipLaunchKernelGGL(rrt_env_kernel, dim3((uint32_t)grid), dim3(256), 0, stream, env, n, dirs, rgb);
+  return hipGetLastError();
+}
+hipError_t rrt_launch_disk(const DDisk& disk, double m, uint64_t n, const double* r_m, const double* g, float* rgb,
+                           hipStream_t stream) {
+  uint64_t grid = (n + 255) / 256;
+  if (grid > 8192) grid = 8192;
+  if (grid == 0) grid = 1;
+  hipLaunchKernelGGL(rrt_disk_kernel, dim3((uint32_t)grid), dim3(256), 0, stream, disk, m, n, r_m, g, rgb);
   return hipGetLastError();
 }
 hipError_t rrt_launch_tonemap(uint32_t n, const float* rgb, uint32_t* out, float exposure, float inv_gamma,

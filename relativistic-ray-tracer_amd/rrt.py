@@ -87,11 +87,14 @@ class SpacetimeDesc(C.Structure):
 
 
 RRT_DISK_NO_REDSHIFT = 1  # rrt_disk_desc.flags
+RRT_DISK_BLACKBODY = 4    # the blackbody disk; bit 1 is unassigned and rejected
+RRT_DISK_PROFILE_POWER, RRT_DISK_PROFILE_ZERO_TORQUE = 0, 1  # rrt_disk_desc.profile
+DISK_PROFILES = {"power": RRT_DISK_PROFILE_POWER, "zero-torque": RRT_DISK_PROFILE_ZERO_TORQUE}
 
 
 class DiskDesc(C.Structure):  # rrt_disk_desc
     _fields_ = [("r_in", C.c_double), ("r_out", C.c_double), ("emission", C.c_float * 3), ("flags", C.c_uint32),
-                ("reserved", C.c_uint32 * 4)]
+                ("temperature", C.c_float), ("profile", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
 class RenderParams(C.Structure):
@@ -144,7 +147,7 @@ EXPORTS = ["rrt_abi_version", "rrt_create", "rrt_destroy", "rrt_last_error", "rr
            "rrt_get_occluders", "rrt_group_create", "rrt_group_render", "rrt_group_destroy", "rrt_libm_eval",
            "rrt_set_proof_audit", "rrt_get_proof_audit", "rrt_get_search_tree4", "rrt_trace_rays",
            "rrt_trace_rays_device", "rrt_trace_camera", "rrt_trace_camera_device", "rrt_env_eval", "rrt_set_disk",
-           "rrt_get_disk"]
+           "rrt_get_disk", "rrt_disk_eval", "rrt_blackbody_tint"]
 AUDIT_KINDS = ("camera", "shadow", "pixel", "strip", "kerr", "zero")  # include/rrt.h RRT_AUDIT_*
 
 _lib = None
@@ -199,6 +202,9 @@ def lib():
         if hasattr(L, "rrt_set_disk"):  # absent from older builds loaded through RRT_LIB
             L.rrt_set_disk.argtypes = [vp, C.POINTER(DiskDesc)]
             L.rrt_get_disk.argtypes = [vp, C.POINTER(DiskDesc)]
+        if hasattr(L, "rrt_disk_eval"):  # absent from older builds loaded through RRT_LIB
+            L.rrt_disk_eval.argtypes = [vp, vp, vp, C.c_uint64, vp]
+            L.rrt_blackbody_tint.argtypes = [C.c_double, C.POINTER(C.c_float * 3)]
         if hasattr(L, "rrt_set_proof_audit"):  # absent from older builds loaded through RRT_LIB
             L.rrt_set_proof_audit.argtypes = [vp, C.c_int]
             L.rrt_get_proof_audit.argtypes = [vp, vp]
@@ -358,6 +364,16 @@ def kerr_frame(axis=(0.0, 1.0, 0.0)):
     return out
 
 
+def blackbody_tint(temperature):
+    """The three-wavelength Planck colour of a blackbody at `temperature` Kelvin (1000..1e6) normalised to
+    G = 1, a float tuple (rrt_blackbody_tint): the physical emission of a blackbody disk."""
+    out = (C.c_float * 3)()
+    rc = lib().rrt_blackbody_tint(float(temperature), C.byref(out))
+    if rc != RRT_OK:
+        raise RRTError(rc, "blackbody_tint: the temperature must lie in [1000, 1e6] K")
+    return tuple(out)
+
+
 def load_exr(path):
     """Environment map texels [h][w][3] float32 (rrt_exr_load: main.cpp's load_exr)."""
     t = C.POINTER(C.c_float)()
@@ -460,10 +476,14 @@ class Renderer:
     LIBM_FN = {"sin": 0, "cos": 1, "acos": 2, "atan2": 3, "sinf": 4, "cosf": 5, "exp": 6, "log": 7, "erf": 8,
                "atan": 9, "tan": 10}
 
-    def set_disk(self, r_in=0.0, r_out=None, emission=(1.0, 1.0, 1.0), redshift=True):
+    def set_disk(self, r_in=0.0, r_out=None, emission=None, redshift=True, temperature=None, profile="power"):
         """The thin accretion disk of a Kerr hole (rrt_set_disk): the annulus r_in..r_out
         (in M; r_in=0: the prograde ISCO of the spin in force) of the equatorial plane, radiance
-        emission x (r_in / r)^3 x g^4; redshift=False: g = 1.  set_disk(None) removes it."""
+        emission x (r_in / r)^3 x g^4; redshift=False: g = 1.  set_disk(None) removes it.
+        temperature (Kelvin, 1000..1e6): the blackbody disk with the temperature profile
+        "power" (T ~ r^-3/4, `temperature` at r_in) or "zero-torque" (`temperature` at its peak,
+        r = 49/36 r_in); emission is then the colour of gas at `temperature` seen at g = 1.
+        emission=None: (1, 1, 1), with a temperature blackbody_tint(temperature)."""
         if r_in is None:
             self._chk(lib().rrt_set_disk(self.h, None))
             return
@@ -471,8 +491,14 @@ class Renderer:
             raise ValueError("set_disk needs r_out")
         d = DiskDesc()
         d.r_in, d.r_out = r_in, r_out
-        d.emission[0], d.emission[1], d.emission[2] = emission
         d.flags = 0 if redshift else RRT_DISK_NO_REDSHIFT
+        if temperature is not None:
+            d.flags |= RRT_DISK_BLACKBODY
+            d.temperature = temperature
+            d.profile = DISK_PROFILES[profile] if isinstance(profile, str) else profile
+            if emission is None and 1000.0 <= d.temperature <= 1e6:  # (else rrt_set_disk rejects the descriptor)
+                emission = blackbody_tint(d.temperature)  # of the float the descriptor holds
+        d.emission[0], d.emission[1], d.emission[2] = (1.0, 1.0, 1.0) if emission is None else emission
         self._chk(lib().rrt_set_disk(self.h, C.byref(d)))
 
     def get_disk(self):
@@ -480,8 +506,23 @@ class Renderer:
         d = DiskDesc()
         if not lib().rrt_get_disk(self.h, C.byref(d)):
             return None
-        return {"r_in": d.r_in, "r_out": d.r_out, "emission": tuple(d.emission),
-                "redshift": not (d.flags & RRT_DISK_NO_REDSHIFT)}
+        out = {"r_in": d.r_in, "r_out": d.r_out, "emission": tuple(d.emission),
+               "redshift": not (d.flags & RRT_DISK_NO_REDSHIFT)}
+        if d.flags & RRT_DISK_BLACKBODY:
+            out["temperature"] = d.temperature
+            out["profile"] = {v: k for k, v in DISK_PROFILES.items()}[d.profile]
+        return out
+
+    def disk_eval(self, r_m, g):
+        """The device's colour rule of the disk in force (rrt_disk_eval) at the
+        Boyer-Lindquist radii r_m [n] (in M) and redshifts g [n]: float32 [n, 3]."""
+        r_m = np.ascontiguousarray(np.asarray(r_m, np.float64).ravel())
+        g = np.ascontiguousarray(np.asarray(g, np.float64).ravel())
+        if len(r_m) != len(g):
+            raise ValueError("disk_eval needs as many redshifts as radii")
+        out = np.zeros((len(r_m), 3), np.float32)
+        self._chk(lib().rrt_disk_eval(self.h, _p(r_m), _p(g), len(r_m), _p(out)))
+        return out
 
     def libm_eval(self, fn, a, b=None):
         """The device's restated host-libm function `fn` (rrt_glibm.h) on float64 arrays a (, b)."""
