@@ -155,7 +155,8 @@ int rrt_set_spacetime(rrt_ctx* ctx, const rrt_spacetime_desc* st);
  * plane; a camera ray that reaches the disk returns emission x (r_in / r)^3 x g^4, g the redshift
  * from the photon's L_z at the crossing; every other ray that reaches it ends there (a shadow ray is
  * occluded; the radiance enters where a hit's emission does: hemisphere-sampled direct light and
- * the bounce after a delta BSDF).  The disk is no light: it is not importance-sampled.
+ * the bounce after a delta BSDF).  The disk is in no light list; RRT_DISK_LIGHT (below) has it
+ * importance-sampled.
  * Rendered by one build of the general per-pixel-loop kernel (any depth, every ray marched exactly,
  * no proofs; with or without RRT_SPACETIME_LENSED_SKY).  At render or trace time RRT_E_INVALID for a
  * Schwarzschild-kind spacetime (its stepper carries no momentum: take RRT_METRIC_KERR with spin
@@ -171,9 +172,18 @@ int rrt_set_spacetime(rrt_ctx* ctx, const rrt_spacetime_desc* st);
  * and 465 nm, the pixel is emission x the Planck ratio B(g T) / B(temperature): `emission` is the
  * RGB radiance of gas at `temperature` seen at g = 1 (rrt_blackbody_tint gives the physical one).
  * Rendered by a build of its own; the ray-query records are the plain disk's.  Without the flag every
- * output is what it was. */
+ * output is what it was.
+ * RRT_DISK_LIGHT samples the disk as a light under importance-sampled direct light:
+ * after the listed lights, ns_area_light points of the annulus, uniform in its coordinate area, each
+ * with the flat direction and solid-angle density from the shading point and the disk's radiance
+ * where the bent ray along that direction really meets the disk (nothing for a primitive in front,
+ * a capture or an escape); the term is normalised by its own sample count, so the listed lights'
+ * term and draws are unchanged.  Light that reaches a surface from outside the disk's flat image
+ * is left out.  Builds of their own (plain and blackbody); with direct_hemisphere, or at depth 0,
+ * the flag changes nothing.  Without the flag every output is what it was. */
 enum { RRT_DISK_NO_REDSHIFT = 1u << 0,   /* g = 1: the bare profile */
-       RRT_DISK_BLACKBODY = 1u << 2 };   /* bit 1 is unassigned and rejected */
+       RRT_DISK_BLACKBODY = 1u << 2,     /* bit 1 is unassigned and rejected */
+       RRT_DISK_LIGHT = 1u << 4 };       /* importance-sample the disk as a light; bit 3 is unassigned and rejected */
 enum { RRT_DISK_PROFILE_POWER = 0, RRT_DISK_PROFILE_ZERO_TORQUE = 1 };
 typedef struct {
   double r_in, r_out;         /* in M; r_in == 0: the prograde ISCO of the spin in force at launch */
@@ -490,6 +500,13 @@ int rrt_env_eval(rrt_ctx* ctx, const double* dirs, uint64_t n, float* rgb);
  * without a launch.  Without a disk, or with one invalid for the current spacetime, the errors of a
  * render launch; RRT_E_NO_DEVICE on a host-only context. */
 int rrt_disk_eval(rrt_ctx* ctx, const double* r_m, const double* g, uint64_t n, float* rgb);
+/* The device's sampler of the disk light (rrt_device.h disk_sample) for the disk in
+ * force, with or without RRT_DISK_LIGHT, on n host pairs: the world point p[i] and the draws uv[i]
+ * (u picks the radius, v the azimuth) -> the unit direction wi[i] from p[i] to the sampled point of
+ * the annulus and the flat solid-angle density pdf[i] = d^2 / (area |wi . axis|); an invalid sample
+ * (p in the disk's plane) gives pdf 0.  n == 0 and the errors as rrt_disk_eval. */
+int rrt_disk_sample(rrt_ctx* ctx, const double* p /*[n][3]*/, const double* uv /*[n][2]*/, uint64_t n,
+                    double* wi /*[n][3]*/, float* pdf /*[n]*/);
 /* Host only: the three-wavelength Planck colour of a blackbody at T Kelvin normalised to G = 1,
  * rgb[c] = (float)(W_c (exp(K_G / T) - 1) / (exp(K_c / T) - 1)), W_c = (550 / lambda_c)^5,
  * K_c = 14387768.77 nm K / lambda_c, lambda = 610, 550, 465 nm -- the physical `emission` of a

@@ -10,8 +10,9 @@
 // map along their exit direction) and --disk R_IN R_OUT [--disk-emission R G B]
 // [--disk-no-redshift] (a thin accretion disk, radii in M, R_IN 0 = the ISCO; needs --kerr; DESIGN.md
 // §12) [--disk-temp KELVIN] [--disk-profile power|zero-torque] (the blackbody disk, DESIGN.md §13;
-// without --disk-emission the emission is rrt_blackbody_tint of KELVIN).  The interactive viewer is
-// out of scope: -f is required.  Exit codes follow main.cpp (usage -> 1).
+// without --disk-emission the emission is rrt_blackbody_tint of KELVIN) [--disk-light] (the disk
+// importance-sampled as a light).  The interactive viewer is out of scope: -f is
+// required.  Exit codes follow main.cpp (usage -> 1).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -45,6 +46,7 @@ static void usage(const char* binary) {
   std::printf("  --disk-emission <R> <G> <B>  Disk radiance at R_IN (default 1 1 1)   --disk-no-redshift  g = 1\n");
   std::printf("  --disk-temp <KELVIN>  Blackbody disk: temperature in [1000, 1e6] K; the emission defaults to its Planck colour\n");
   std::printf("  --disk-profile <power|zero-torque>  Blackbody disk: T ~ r^-3/4, or the zero-torque profile peaking at KELVIN\n");
+  std::printf("  --disk-light     Sample the disk as a light under importance-sampled direct light; needs --disk\n");
   std::printf("  -h               Print this help message\n");
 }
 
@@ -61,7 +63,7 @@ int main(int argc, char** argv) {
   unsigned long long seed = 0;
   int device = 0;
   std::vector<int> devices;  // --devices: several GPUs (rrt_group)
-  bool to_file = false, lensed_sky = false, has_disk = false, has_emission = false, has_temp = false, has_profile = false;
+  bool to_file = false, lensed_sky = false, has_disk = false, has_emission = false, has_temp = false, has_profile = false, disk_light = false;
   rrt_disk_desc disk;
   std::memset(&disk, 0, sizeof(disk));
   disk.emission[0] = disk.emission[1] = disk.emission[2] = 1.0f;
@@ -132,6 +134,7 @@ int main(int argc, char** argv) {
       has_profile = true;
     }
     else if (a == "--disk-no-redshift") { disk.flags |= RRT_DISK_NO_REDSHIFT; }
+    else if (a == "--disk-light") { disk.flags |= RRT_DISK_LIGHT; disk_light = true; }
     else if (a == "--kerr") {
       need(i, 1);
       kerr_spin = std::atof(argv[++i]);
@@ -148,6 +151,10 @@ int main(int argc, char** argv) {
   if (scene_path.empty()) { usage(argv[0]); return 1; }
   if ((has_temp || has_profile) && !has_disk) {
     std::fprintf(stderr, "[rrt_render] --disk-temp and --disk-profile need --disk R_IN R_OUT\n");
+    return 1;
+  }
+  if (disk_light && !has_disk) {
+    std::fprintf(stderr, "[rrt_render] --disk-light needs --disk R_IN R_OUT\n");
     return 1;
   }
   if (has_profile && !has_temp) {

@@ -854,9 +854,16 @@ constexpr int V_KERR_DISK = 7;
 // V_KERR_DISK_BB: V_KERR_DISK with the blackbody colour rule (RRT_DISK_BLACKBODY) in
 // place of the plain one: a build of its own, so that V_KERR_DISK keeps its registers and scratch.
 constexpr int V_KERR_DISK_BB = 8;
+// V_KERR_DISK_LIGHT / V_KERR_DISK_BB_LIGHT: the two disk builds with the disk importance-sampled as a
+// light (RRT_DISK_LIGHT; rrt_integrator.h disk_direct): builds of their own, so that
+// their parents keep their registers and scratch.  Everywhere else they behave as their parents.
+constexpr int V_KERR_DISK_LIGHT = 9;
+constexpr int V_KERR_DISK_BB_LIGHT = 10;
 __host__ __device__ constexpr bool is_lean(int v) { return v == 1 || v == 2; }
 __host__ __device__ constexpr bool is_sky(int v) { return v == V_SKY || v == V_KERR_SKY; }
-__host__ __device__ constexpr bool is_disk(int v) { return v == V_KERR_DISK || v == V_KERR_DISK_BB; }
+__host__ __device__ constexpr bool is_disk_light(int v) { return v == V_KERR_DISK_LIGHT || v == V_KERR_DISK_BB_LIGHT; }
+__host__ __device__ constexpr bool is_disk_bb(int v) { return v == V_KERR_DISK_BB || v == V_KERR_DISK_BB_LIGHT; }
+__host__ __device__ constexpr bool is_disk(int v) { return v == V_KERR_DISK || v == V_KERR_DISK_BB || is_disk_light(v); }
 __host__ __device__ constexpr bool is_kerr_build(int v) { return v == V_KERR || v == V_KERR_SKY || is_disk(v); }
 __host__ __device__ constexpr int general_of(int v) {  // non-LEAN build
   return v == V_KERR || v == V_SW || is_sky(v) || is_disk(v) ? v : 0;
@@ -1134,6 +1141,25 @@ __device__ __forceinline__ spec disk_rgb(const DDisk& dd, double r, double g) {
     f[k] = dd.emission[k] * (float)ratio;
   }
   return S(f[0], f[1], f[2]);
+}
+// The disk as a light (RRT_DISK_LIGHT): a point of the annulus drawn uniformly in the
+// coordinate area of the Kerr-Schild plane (x^2 + y^2 = r^2 + a^2: rho^2 uniform in rho_in2 ..
+// rho_in2 + rho_span), the flat direction wi from world point p to it and the flat solid-angle
+// density pdf = d^2 / (area |wi . ez|) -- both faces emit: no sign test.  + - x / sqrt, one
+// rrt_glibm_cos and one rrt_glibm_sin.  True iff pdf is finite and > 0 (p in the plane: false).
+__device__ __forceinline__ bool disk_sample(const DHole& h, const DDisk& dd, v3 p, double u, double v, v3& wi, float& pdf) {
+  const double rho = xsqrt(dd.rho_in2 + u * dd.rho_span);
+  const double phi = (2.0 * PI_D) * v;
+  const double x = rho * rrt_glibm_cos(phi);
+  const double y = rho * rrt_glibm_sin(phi);
+  const v3 P = kerr_world(h, V(x, y, 0.0));
+  const v3 dv = P - p;
+  const double d2 = norm2(dv);
+  const double inv = xdiv(1.0, xsqrt(d2));
+  wi = V(dv.x * inv, dv.y * inv, dv.z * inv);
+  const double c = fabs(dot(wi, ld3(h.ez)));
+  pdf = (float)xdiv(d2, dd.area * c);
+  return isfinite(pdf) && pdf > 0.0f;
 }
 // the march of query_kerr (no proof).  EXIT: an escaping photon goes on to its exit direction (*xr).
 // DISK: with kp.disk.on every step is tested against the accretion disk next to its chord's segment

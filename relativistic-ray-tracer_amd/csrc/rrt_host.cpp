@@ -40,6 +40,8 @@ hipError_t rrt_launch_trace(const KParams* d_kp, const TraceArgs& a, int kerr, i
                             hipStream_t stream);
 hipError_t rrt_launch_disk(const DDisk& disk, double m, uint64_t n, const double* r_m, const double* g, float* rgb,
                            hipStream_t stream);
+hipError_t rrt_launch_disk_sample(const DHole& hole, const DDisk& disk, uint64_t n, const double* p, const double* uv,
+                                  double* wi, float* pdf, hipStream_t stream);
 hipError_t rrt_launch_trace_disk(const KParams* d_kp, const TraceArgs& a, int any, int exit, hipStream_t stream);
 hipError_t rrt_launch_unpack(const uint32_t* tiles, uint32_t n_tiles, uint32_t ts, uint32_t fw, uint32_t fh,
                              const float* rgb_p, const int32_t* cnt_p, float* rgb, int32_t* cnt, hipStream_t stream);
@@ -1287,7 +1289,7 @@ extern "C" int rrt_set_disk(rrt_ctx* c, const rrt_disk_desc* d) {
     if (!(std::isfinite(d->emission[k]) && d->emission[k] >= 0.0f))
       return fail(c, RRT_E_INVALID, "disk emission must be finite and >= 0");
   if (!(d->r_out > d->r_in)) return fail(c, RRT_E_INVALID, "disk needs r_out > r_in");
-  if (d->flags & ~(uint32_t)(RRT_DISK_NO_REDSHIFT | RRT_DISK_BLACKBODY))
+  if (d->flags & ~(uint32_t)(RRT_DISK_NO_REDSHIFT | RRT_DISK_BLACKBODY | RRT_DISK_LIGHT))
     return fail(c, RRT_E_INVALID, "unknown rrt_disk_desc flags");
   if (d->flags & RRT_DISK_BLACKBODY) {  // DESIGN.md §13; the range keeps every intermediate of the rule finite
     if (!(std::isfinite(d->temperature) && d->temperature >= (float)RRT_BB_T_MIN && d->temperature <= (float)RRT_BB_T_MAX))
@@ -1342,6 +1344,13 @@ static int fill_disk_params(rrt_ctx* c, KParams& kp) {
     d.temperature = (double)c->disk.temperature;
     rrt_bb_constants(d.temperature, d.bb_k, d.bb_n);
   }
+  // the annulus in the Kerr-Schild plane (x^2 + y^2 = r^2 + a^2), for disk_sample;
+  // light: the builds V_KERR_DISK_LIGHT / V_KERR_DISK_BB_LIGHT
+  d.rho_in2 = d.r_in2 + h.a2;
+  d.rho_span = d.r_out2 - d.r_in2;
+  d.area = kPI * d.rho_span;
+  d.light = (c->disk.flags & RRT_DISK_LIGHT) ? 1u : 0u;
+  d.pad = 0u;
   const double e2 = d.r_out2 + h.a2;  // |q|^2 on the plane at r_out
   if (e2 > kp.hole.r_esc2) kp.hole.r_esc2 = e2;
   return RRT_OK;
@@ -1699,7 +1708,8 @@ static int launch(rrt_ctx* c, const rrt_render_params* p, const uint32_t* tiles,
     return fail(c, RRT_E_INVALID, "RRT_RENDER_WAVEFRONT (the path pool kernel) renders max_ray_depth >= 2 "
                                   "Schwarzschild frames without counters or switches, n_lights x ns_area_light < 2048");
   const bool pixel_loop = !path_pool && ((deep && !deep_sample) || (p->flags & RRT_RENDER_PIXEL_LOOP) || sw || sky || disk);
-  const int lean = disk ? (kp.disk.blackbody ? 8 /* V_KERR_DISK_BB */ : 7 /* V_KERR_DISK */)
+  const int lean = disk ? (kp.disk.light ? (kp.disk.blackbody ? 10 /* V_KERR_DISK_BB_LIGHT */ : 9 /* V_KERR_DISK_LIGHT */)
+                                         : (kp.disk.blackbody ? 8 /* V_KERR_DISK_BB */ : 7 /* V_KERR_DISK */))
                  : sky ? (kerr ? 6 /* V_KERR_SKY */ : 5 /* V_SKY */)
                  : kerr ? 3 /* V_KERR */
                  : sw ? 4 /* V_SW */
@@ -2230,6 +2240,35 @@ extern "C" int rrt_disk_eval(rrt_ctx* c, const double* r_m, const double* g, uin
   HIPCHK(c, hipMemcpy(dg, g, sizeof(double) * n, hipMemcpyHostToDevice));
   HIPCHK(c, rrt_launch_disk(probe.disk, probe.hole.m, n, dr, dg, dc, (hipStream_t)0));
   HIPCHK(c, hipMemcpy(rgb, dc, sizeof(float) * 3 * n, hipMemcpyDeviceToHost));
+  return RRT_OK;
+}
+
+extern "C" int rrt_disk_sample(rrt_ctx* c, const double* p, const double* uv, uint64_t n, double* wi, float* pdf) {
+  if (!c || (n && (!p || !uv || !wi || !pdf))) return fail(c, RRT_E_INVALID, "bad argument");
+  if (!c->has_disk) return fail(c, RRT_E_INVALID, "no accretion disk (rrt_set_disk)");
+  KParams probe{};  // the disk's device constants as a launch fills them
+  probe.hole = c->hole;
+  if (int rc = fill_disk_params(c, probe)) return rc;
+  if (c->device < 0) return fail(c, RRT_E_NO_DEVICE, "no device");
+  if (n == 0) return RRT_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  double* dp = nullptr;
+  double* du = nullptr;
+  double* dw = nullptr;
+  float* df = nullptr;
+  struct Free {
+    void** p[4];
+    ~Free() { for (void** q : p) if (*q) (void)hipFree(*q); }
+  } guard{{(void**)&dp, (void**)&du, (void**)&dw, (void**)&df}};
+  HIPCHK(c, hipMalloc(&dp, sizeof(double) * 3 * n));
+  HIPCHK(c, hipMalloc(&du, sizeof(double) * 2 * n));
+  HIPCHK(c, hipMalloc(&dw, sizeof(double) * 3 * n));
+  HIPCHK(c, hipMalloc(&df, sizeof(float) * n));
+  HIPCHK(c, hipMemcpy(dp, p, sizeof(double) * 3 * n, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(du, uv, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
+  HIPCHK(c, rrt_launch_disk_sample(probe.hole, probe.disk, n, dp, du, dw, df, (hipStream_t)0));
+  HIPCHK(c, hipMemcpy(wi, dw, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(pdf, df, sizeof(float) * n, hipMemcpyDeviceToHost));
   return RRT_OK;
 }
 

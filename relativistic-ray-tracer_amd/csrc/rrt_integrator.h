@@ -13,12 +13,12 @@ namespace rrt {
 // ray went if it hit nothing (they only).
 // The disk builds (V_KERR_DISK; V_KERR_DISK_BB, §13: the blackbody colour) run the
 // exit-mode march with the disk test; its far march runs only where xr is given (the lensed sky's rule
-// in force).  dk: a hit that is the disk.
+// in force).  dk: a hit that is the disk.  Their _LIGHT builds (§14) trace as their parents.
 template <bool ANY, bool COUNT, bool DEEP, int LEAN>
 __device__ __forceinline__ bool trace(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn, ExitRec* xr = nullptr,
                                       DiskRec* dk = nullptr) {
   return query<ANY, COUNT, is_kerr_build(LEAN), is_lean(LEAN), is_sky(LEAN) || is_disk(LEAN), is_disk(LEAN),
-               LEAN == V_KERR_DISK_BB>(kp, o, d, is, cn, false, nullptr, xr, dk);
+               is_disk_bb(LEAN)>(kp, o, d, is, cn, false, nullptr, xr, dk);
 }
 // the emission a ray picks up at its hit: the hit primitive's BSDF's, or the disk's radiance
 __device__ __forceinline__ spec hit_emission(const KParams& kp, const Isect& is, const DiskRec& dk) {
@@ -83,9 +83,41 @@ __device__ spec direct_hemisphere(const KParams& kp, Rng& g, const Isect& is, Co
   return ((L * 2.0f) * (float)PI_D) / (float)num;
 }
 
+// The disk importance-sampled as a light (RRT_DISK_LIGHT; the _LIGHT disk builds):
+// ns_area_light samples of the annulus's flat image (disk_sample; two draws each, as an area light's),
+// each evaluated by the closest-hit march along the bent ray: the disk's radiance where that ray
+// really meets it, nothing for a primitive in front, a capture or an escape.  Drawn after every listed
+// light and normalised by its own sample count, so direct_importance's term and draws stay as they are.
+template <bool COUNT, int LEAN, bool DEEP>
+__device__ __forceinline__ spec disk_direct(const KParams& kp, Rng& g, const Isect& is, Counters& cn) {
+  const DBsdf b = kp.bsdfs[is.bsdf];
+  spec L = S(0, 0, 0);
+  const int num = (int)kp.ns_area_light;
+  if (num == 0) return L;
+  for (int i = 0; i < num; ++i) {
+    double u, v;
+    g.grid(u, v);
+    v3 wi_world; float pdf;
+    if (!disk_sample(kp.hole, kp.disk, is.hit_p, u, v, wi_world, pdf)) continue;
+    const Frame f = coord_space(is.n);
+    v3 w_in = to_local(f, wi_world);
+    if (w_in.z < 0) continue;
+    Isect is2;
+    DiskRec dk = {S(0, 0, 0), false};
+    if (!trace<false, COUNT, DEEP, LEAN>(kp, is.hit_p + smul(EPS_D, wi_world), wi_world, &is2, cn, nullptr, &dk) || !dk.hit)
+      continue;
+    L = L + ((dk.rgb * bsdf_f<LEAN>(b, to_local(f, is.w_out), w_in)) * (float)w_in.z) / pdf;
+  }
+  return L / (float)num;
+}
+
 template <bool COUNT, int LEAN, bool DEEP>
 __device__ __forceinline__ spec one_bounce(const KParams& kp, Rng& g, const Isect& is, Counters& cn) {
   if (is_lean(LEAN)) return direct_importance<COUNT, LEAN, DEEP>(kp, g, is, cn);
+  if (is_disk_light(LEAN) && kp.disk.light && !kp.direct_hemisphere) {
+    const spec Ll = direct_importance<COUNT, LEAN, DEEP>(kp, g, is, cn);  // the listed lights first: their draws
+    return Ll + disk_direct<COUNT, LEAN, DEEP>(kp, g, is, cn);
+  }
   return kp.direct_hemisphere ? direct_hemisphere<COUNT, general_of(LEAN), DEEP>(kp, g, is, cn)
                               : direct_importance<COUNT, general_of(LEAN), DEEP>(kp, g, is, cn);
 }

@@ -189,6 +189,13 @@ struct DDisk {
   double bb_n[3];         // N_c = exp(K_c / temperature) - 1 (rrt_glibm_exp on the host)
   uint32_t blackbody;     // 1: RRT_DISK_BLACKBODY (rendered by V_KERR_DISK_BB)
   uint32_t profile;       // RRT_DISK_PROFILE_*
+  // the disk as a light (RRT_DISK_LIGHT; rrt_device.h disk_sample): the annulus in the
+  // Kerr-Schild plane, where x^2 + y^2 = r^2 + a^2; filled for every disk (rrt_disk_sample)
+  double rho_in2;         // (r_in M)^2 + a^2
+  double rho_span;        // (r_out M)^2 - (r_in M)^2
+  double area;            // PI_D x rho_span: the annulus's coordinate area
+  uint32_t light;         // 1: RRT_DISK_LIGHT (rendered by V_KERR_DISK_LIGHT / V_KERR_DISK_BB_LIGHT)
+  uint32_t pad;
 };
 
 #define RRT_MAX_QUEUES 8

@@ -230,6 +230,19 @@ __global__ void rrt_disk_kernel(const DDisk disk, double m, uint64_t n, const do
     rgb[3 * k] = s.r; rgb[3 * k + 1] = s.g; rgb[3 * k + 2] = s.b;
   }
 }
+// The disk light's sampler as disk_direct evaluates it (rrt_device.h disk_sample) on n
+// shading points p [n][3] and draws uv [n][2]: rrt_disk_sample, the checker's handle on points and
+// draws no frame reaches (tests/test_gpu_disk_light.py).  An invalid sample: pdf 0.
+__global__ void rrt_disk_sample_kernel(const DHole hole, const DDisk disk, uint64_t n, const double* p, const double* uv,
+                                       double* wi, float* pdf) {
+  for (uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; k < n; k += (uint64_t)gridDim.x * blockDim.x) {
+    rrt::v3 w;
+    float f;
+    const bool ok = rrt::disk_sample(hole, disk, rrt::V(p[3 * k], p[3 * k + 1], p[3 * k + 2]), uv[2 * k], uv[2 * k + 1], w, f);
+    wi[3 * k] = w.x; wi[3 * k + 1] = w.y; wi[3 * k + 2] = w.z;
+    pdf[k] = ok ? f : 0.0f;
+  }
+}
 
 // ------------------------------------------------------------------ launch shims (C++ linkage)
 // Kernel selection: deep / counting variants are built once (1 wave per SIMD budget); the
@@ -250,6 +263,10 @@ hipError_t rrt_launch_render(const KParams& kp, const KParams* d_kp, int deep, i
     RRT_LAUNCH(true, false, rrt::V_KERR_DISK, 2);
   } else if (lean == rrt::V_KERR_DISK_BB) {  // ... with the blackbody colour: a build of its own
     RRT_LAUNCH(true, false, rrt::V_KERR_DISK_BB, 2);
+  } else if (lean == rrt::V_KERR_DISK_LIGHT) {  // ... with the disk sampled as a light: builds of their own
+    RRT_LAUNCH(true, false, rrt::V_KERR_DISK_LIGHT, 2);
+  } else if (lean == rrt::V_KERR_DISK_BB_LIGHT) {
+    RRT_LAUNCH(true, false, rrt::V_KERR_DISK_BB_LIGHT, 2);
   } else if (lean == rrt::V_SW) {  // the reference's switches as run-time flags: one bounce-capable build
     if (count) RRT_LAUNCH(true, true, rrt::V_SW, 1); else RRT_LAUNCH(true, false, rrt::V_SW, 1);
   } else if (lean == rrt::V_KERR) {  // the Kerr builds (general integrator)
@@ -321,6 +338,14 @@ hipError_t rrt_launch_disk(const DDisk& disk, double m, uint64_t n, const double
   if (grid > 8192) grid = 8192;
   if (grid == 0) grid = 1;
   hipLaunchKernelGGL(rrt_disk_kernel, dim3((uint32_t)grid), dim3(256), 0, stream, disk, m, n, r_m, g, rgb);
+  return hipGetLastError();
+}
+hipError_t rrt_launch_disk_sample(const DHole& hole, const DDisk& disk, uint64_t n, const double* p, const double* uv,
+                                  double* wi, float* pdf, hipStream_t stream) {
+  uint64_t grid = (n + 255) / 256;
+  if (grid > 8192) grid = 8192;
+  if (grid == 0) grid = 1;
+  hipLaunchKernelGGL(rrt_disk_sample_kernel, dim3((uint32_t)grid), dim3(256), 0, stream, hole, disk, n, p, uv, wi, pdf);
   return hipGetLastError();
 }
 hipError_t rrt_launch_tonemap(uint32_t n, const float* rgb, uint32_t* out, float exposure, float inv_gamma,

@@ -88,6 +88,7 @@ class SpacetimeDesc(C.Structure):
 
 RRT_DISK_NO_REDSHIFT = 1  # rrt_disk_desc.flags
 RRT_DISK_BLACKBODY = 4    # the blackbody disk; bit 1 is unassigned and rejected
+RRT_DISK_LIGHT = 16       # the disk importance-sampled as a light; bit 3 is unassigned and rejected
 RRT_DISK_PROFILE_POWER, RRT_DISK_PROFILE_ZERO_TORQUE = 0, 1  # rrt_disk_desc.profile
 DISK_PROFILES = {"power": RRT_DISK_PROFILE_POWER, "zero-torque": RRT_DISK_PROFILE_ZERO_TORQUE}
 
@@ -147,7 +148,7 @@ EXPORTS = ["rrt_abi_version", "rrt_create", "rrt_destroy", "rrt_last_error", "rr
            "rrt_get_occluders", "rrt_group_create", "rrt_group_render", "rrt_group_destroy", "rrt_libm_eval",
            "rrt_set_proof_audit", "rrt_get_proof_audit", "rrt_get_search_tree4", "rrt_trace_rays",
            "rrt_trace_rays_device", "rrt_trace_camera", "rrt_trace_camera_device", "rrt_env_eval", "rrt_set_disk",
-           "rrt_get_disk", "rrt_disk_eval", "rrt_blackbody_tint"]
+           "rrt_get_disk", "rrt_disk_eval", "rrt_blackbody_tint", "rrt_disk_sample"]
 AUDIT_KINDS = ("camera", "shadow", "pixel", "strip", "kerr", "zero")  # include/rrt.h RRT_AUDIT_*
 
 _lib = None
@@ -205,6 +206,8 @@ def lib():
         if hasattr(L, "rrt_disk_eval"):  # absent from older builds loaded through RRT_LIB
             L.rrt_disk_eval.argtypes = [vp, vp, vp, C.c_uint64, vp]
             L.rrt_blackbody_tint.argtypes = [C.c_double, C.POINTER(C.c_float * 3)]
+        if hasattr(L, "rrt_disk_sample"):  # absent from older builds loaded through RRT_LIB
+            L.rrt_disk_sample.argtypes = [vp, vp, vp, C.c_uint64, vp, vp]
         if hasattr(L, "rrt_set_proof_audit"):  # absent from older builds loaded through RRT_LIB
             L.rrt_set_proof_audit.argtypes = [vp, C.c_int]
             L.rrt_get_proof_audit.argtypes = [vp, vp]
@@ -476,14 +479,17 @@ class Renderer:
     LIBM_FN = {"sin": 0, "cos": 1, "acos": 2, "atan2": 3, "sinf": 4, "cosf": 5, "exp": 6, "log": 7, "erf": 8,
                "atan": 9, "tan": 10}
 
-    def set_disk(self, r_in=0.0, r_out=None, emission=None, redshift=True, temperature=None, profile="power"):
+    def set_disk(self, r_in=0.0, r_out=None, emission=None, redshift=True, temperature=None, profile="power",
+                 light=False):
         """The thin accretion disk of a Kerr hole (rrt_set_disk): the annulus r_in..r_out
         (in M; r_in=0: the prograde ISCO of the spin in force) of the equatorial plane, radiance
         emission x (r_in / r)^3 x g^4; redshift=False: g = 1.  set_disk(None) removes it.
         temperature (Kelvin, 1000..1e6): the blackbody disk with the temperature profile
         "power" (T ~ r^-3/4, `temperature` at r_in) or "zero-torque" (`temperature` at its peak,
         r = 49/36 r_in); emission is then the colour of gas at `temperature` seen at g = 1.
-        emission=None: (1, 1, 1), with a temperature blackbody_tint(temperature)."""
+        emission=None: (1, 1, 1), with a temperature blackbody_tint(temperature).
+        light=True (RRT_DISK_LIGHT): importance-sampled direct light samples the disk too,
+        ns_area_light points of its flat image, after the listed lights."""
         if r_in is None:
             self._chk(lib().rrt_set_disk(self.h, None))
             return
@@ -491,7 +497,7 @@ class Renderer:
             raise ValueError("set_disk needs r_out")
         d = DiskDesc()
         d.r_in, d.r_out = r_in, r_out
-        d.flags = 0 if redshift else RRT_DISK_NO_REDSHIFT
+        d.flags = (0 if redshift else RRT_DISK_NO_REDSHIFT) | (RRT_DISK_LIGHT if light else 0)
         if temperature is not None:
             d.flags |= RRT_DISK_BLACKBODY
             d.temperature = temperature
@@ -502,7 +508,8 @@ class Renderer:
         self._chk(lib().rrt_set_disk(self.h, C.byref(d)))
 
     def get_disk(self):
-        """The disk in force as a dict (r_in resolved: 0 -> the ISCO of a Kerr spacetime), or None."""
+        """The disk in force as a dict (r_in resolved: 0 -> the ISCO of a Kerr spacetime), or None.
+        "temperature" and "profile" are there for a blackbody disk, "light": True for a disk light."""
         d = DiskDesc()
         if not lib().rrt_get_disk(self.h, C.byref(d)):
             return None
@@ -511,7 +518,22 @@ class Renderer:
         if d.flags & RRT_DISK_BLACKBODY:
             out["temperature"] = d.temperature
             out["profile"] = {v: k for k, v in DISK_PROFILES.items()}[d.profile]
+        if d.flags & RRT_DISK_LIGHT:
+            out["light"] = True
         return out
+
+    def disk_sample(self, p, uv):
+        """The device's sampler of the disk light (rrt_disk_sample) for the disk in force,
+        at the world points p [n, 3] with the draws uv [n, 2]: (wi float64 [n, 3], pdf float32 [n]); an
+        invalid sample has pdf 0."""
+        p = np.ascontiguousarray(np.asarray(p, np.float64).reshape(-1, 3))
+        uv = np.ascontiguousarray(np.asarray(uv, np.float64).reshape(-1, 2))
+        if len(p) != len(uv):
+            raise ValueError("disk_sample needs as many draws as points")
+        wi = np.zeros((len(p), 3), np.float64)
+        pdf = np.zeros(len(p), np.float32)
+        self._chk(lib().rrt_disk_sample(self.h, _p(p), _p(uv), len(p), _p(wi), _p(pdf)))
+        return wi, pdf
 
     def disk_eval(self, r_m, g):
         """The device's colour rule of the disk in force (rrt_disk_eval) at the
