@@ -184,7 +184,10 @@ int rrt_set_spacetime(rrt_ctx* ctx, const rrt_spacetime_desc* st);
 enum { RRT_DISK_NO_REDSHIFT = 1u << 0,   /* g = 1: the bare profile */
        RRT_DISK_BLACKBODY = 1u << 2,     /* bit 1 is unassigned and rejected */
        RRT_DISK_LIGHT = 1u << 4 };       /* importance-sample the disk as a light; bit 3 is unassigned and rejected */
-enum { RRT_DISK_PROFILE_POWER = 0, RRT_DISK_PROFILE_ZERO_TORQUE = 1 };
+/* RRT_DISK_PROFILE_PAGE_THORNE: T^4 follows the Page-Thorne flux of the spin in force at
+ * launch, torque-free at r_in (the ISCO or the caller's larger value); `temperature` is the peak
+ * temperature and the inner edge is black, as under ZERO_TORQUE.  Value 2 is unassigned and rejected. */
+enum { RRT_DISK_PROFILE_POWER = 0, RRT_DISK_PROFILE_ZERO_TORQUE = 1, RRT_DISK_PROFILE_PAGE_THORNE = 3 };
 typedef struct {
   double r_in, r_out;         /* in M; r_in == 0: the prograde ISCO of the spin in force at launch */
   float emission[3];          /* radiance at r = r_in for g = 1; blackbody: of gas at `temperature` for g = 1 */

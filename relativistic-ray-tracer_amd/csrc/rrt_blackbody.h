@@ -14,3 +14,11 @@
 // K_c = RRT_BB_HC_K / lambda_c (one division) and N_c = rrt_glibm_exp(K_c / temperature) - 1, the
 // function the device evaluates (rrt_glibm.h), not the C library's
 void rrt_bb_constants(double temperature, double k[3], double n[3]);
+
+// The constants of the Page-Thorne profile (RRT_DISK_PROFILE_PAGE_THORNE) for spin
+// s = a / M and x0 = sqrt(r_in / M) as the device forms it: ca = 1.5 s, a2 = 2 s, the roots x[3] of
+// x^3 - 3 x + 2 s, d[i] = x0 - x[i], the coefficients c[3] (not finite: 0) and norm = 1 / S(x_peak), the
+// peak found by the fixed 200-round ternary search from [x0, 2 x0].  acos, cos and log are
+// rrt_glibm.h's; S is evaluated in the device's operation order.
+#define RRT_PT_ROUNDS 200
+void rrt_pt_constants(double s, double x0, double* ca, double* a2, double x[3], double d[3], double c[3], double* norm);

@@ -9,7 +9,7 @@
 // axis, default +y; build-defined) and --lensed-sky (escaping rays see the environment
 // map along their exit direction) and --disk R_IN R_OUT [--disk-emission R G B]
 // [--disk-no-redshift] (a thin accretion disk, radii in M, R_IN 0 = the ISCO; needs --kerr; DESIGN.md
-// §12) [--disk-temp KELVIN] [--disk-profile power|zero-torque] (the blackbody disk, DESIGN.md §13;
+// §12) [--disk-temp KELVIN] [--disk-profile power|zero-torque|page-thorne] (the blackbody disk, DESIGN.md §13, §15;
 // without --disk-emission the emission is rrt_blackbody_tint of KELVIN) [--disk-light] (the disk
 // importance-sampled as a light).  The interactive viewer is out of scope: -f is
 // required.  Exit codes follow main.cpp (usage -> 1).
@@ -45,7 +45,8 @@ static void usage(const char* binary) {
   std::printf("  --disk <R_IN> <R_OUT>  Thin accretion disk, radii in M (R_IN 0: the ISCO); needs --kerr\n");
   std::printf("  --disk-emission <R> <G> <B>  Disk radiance at R_IN (default 1 1 1)   --disk-no-redshift  g = 1\n");
   std::printf("  --disk-temp <KELVIN>  Blackbody disk: temperature in [1000, 1e6] K; the emission defaults to its Planck colour\n");
-  std::printf("  --disk-profile <power|zero-torque>  Blackbody disk: T ~ r^-3/4, or the zero-torque profile peaking at KELVIN\n");
+  std::printf("  --disk-profile <power|zero-torque|page-thorne>  Blackbody disk: T ~ r^-3/4, or the zero-torque or the\n"
+              "                   Page-Thorne (spin-dependent) profile peaking at KELVIN\n");
   std::printf("  --disk-light     Sample the disk as a light under importance-sampled direct light; needs --disk\n");
   std::printf("  -h               Print this help message\n");
 }
@@ -130,6 +131,7 @@ int main(int argc, char** argv) {
       const std::string v = argv[++i];
       if (v == "power") disk.profile = RRT_DISK_PROFILE_POWER;
       else if (v == "zero-torque") disk.profile = RRT_DISK_PROFILE_ZERO_TORQUE;
+      else if (v == "page-thorne") disk.profile = RRT_DISK_PROFILE_PAGE_THORNE;
       else { usage(argv[0]); return 1; }
       has_profile = true;
     }

@@ -859,11 +859,19 @@ constexpr int V_KERR_DISK_BB = 8;
 // their parents keep their registers and scratch.  Everywhere else they behave as their parents.
 constexpr int V_KERR_DISK_LIGHT = 9;
 constexpr int V_KERR_DISK_BB_LIGHT = 10;
+// V_KERR_DISK_PT / V_KERR_DISK_PT_LIGHT: builds 8 and 10 with the Page-Thorne temperature profile
+// (RRT_DISK_PROFILE_PAGE_THORNE) as disk_rgb's q: builds of their own, so that the log
+// chain is no run-time branch in their parents.  Everywhere else they behave as their parents.
+constexpr int V_KERR_DISK_PT = 11;
+constexpr int V_KERR_DISK_PT_LIGHT = 12;
 __host__ __device__ constexpr bool is_lean(int v) { return v == 1 || v == 2; }
 __host__ __device__ constexpr bool is_sky(int v) { return v == V_SKY || v == V_KERR_SKY; }
-__host__ __device__ constexpr bool is_disk_light(int v) { return v == V_KERR_DISK_LIGHT || v == V_KERR_DISK_BB_LIGHT; }
-__host__ __device__ constexpr bool is_disk_bb(int v) { return v == V_KERR_DISK_BB || v == V_KERR_DISK_BB_LIGHT; }
-__host__ __device__ constexpr bool is_disk(int v) { return v == V_KERR_DISK || v == V_KERR_DISK_BB || is_disk_light(v); }
+__host__ __device__ constexpr bool is_disk_pt(int v) { return v == V_KERR_DISK_PT || v == V_KERR_DISK_PT_LIGHT; }
+__host__ __device__ constexpr bool is_disk_light(int v) {
+  return v == V_KERR_DISK_LIGHT || v == V_KERR_DISK_BB_LIGHT || v == V_KERR_DISK_PT_LIGHT;
+}
+__host__ __device__ constexpr bool is_disk_bb(int v) { return v == V_KERR_DISK_BB || v == V_KERR_DISK_BB_LIGHT || is_disk_pt(v); }
+__host__ __device__ constexpr bool is_disk(int v) { return v == V_KERR_DISK || is_disk_bb(v) || is_disk_light(v); }
 __host__ __device__ constexpr bool is_kerr_build(int v) { return v == V_KERR || v == V_KERR_SKY || is_disk(v); }
 __host__ __device__ constexpr int general_of(int v) {  // non-LEAN build
   return v == V_KERR || v == V_SW || is_sky(v) || is_disk(v) ? v : 0;
@@ -1029,7 +1037,7 @@ __device__ __forceinline__ void audit_note(const KParams& kp, int k, bool violat
   if (violated) atomicAdd(kp.audit + 2 * k + 1, 1ull);
 }
 __device__ __forceinline__ bool kerr_occluded_proof(const KParams& kp, v3 o, v3 d);
-template <bool ANY, bool COUNT, bool EXIT = false, bool DISK = false, bool BB = false>
+template <bool ANY, bool COUNT, bool EXIT = false, bool DISK = false, bool BB = false, bool PT = false>
 __device__ __forceinline__ bool kerr_march(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn, QRec* qr = nullptr,
                                            ExitRec* xr = nullptr, DiskRec* dk = nullptr);
 template <bool ANY, bool COUNT>
@@ -1090,9 +1098,9 @@ __device__ __forceinline__ bool disk_cross(const DHole& h, const DDisk& dd, v3 q
 // L_z = x p_y - y p_x, so g = E_observed / E_emitted = 1 / (u^t (1 - Omega L_z)), the observer's own
 // constant factor left out; a g that is not finite and positive counts as 0.  The colour is disk_rgb's.
 // g out.
-template <bool BB>
+template <bool BB, bool PT = false>
 __device__ __forceinline__ spec disk_rgb(const DDisk& dd, double r, double g);
-template <bool BB = false>
+template <bool BB = false, bool PT = false>
 __device__ __forceinline__ spec disk_radiance(const DHole& h, const DDisk& dd, double x, double y, double lz, double& g_out) {
   const double r = xsqrt((x * x + y * y) - h.a2);
   double g = 1.0;
@@ -1105,7 +1113,7 @@ __device__ __forceinline__ spec disk_radiance(const DHole& h, const DDisk& dd, d
     if (!(g > 0.0 && isfinite(g))) g = 0.0;
   }
   g_out = g;
-  return disk_rgb<BB>(dd, r, g);
+  return disk_rgb<BB, PT>(dd, r, g);
 }
 // The colour of the disk at radius r (scene units) seen at redshift g (ignored, as 1, with
 // dd.no_redshift).  Plain: emission x (r_in / r)^3 x g^4 (bolometric).  BB (§13,
@@ -1114,7 +1122,13 @@ __device__ __forceinline__ spec disk_radiance(const DHole& h, const DDisk& dd, d
 // is a blackbody at g T (I_nu / nu^3 is invariant: the g^4 is inside), and per channel the Planck
 // ratio (exp(K_c / temperature) - 1) / (exp(K_c / (g T)) - 1) scales emission, the colour of gas at
 // `temperature` seen at g = 1.  Anything not finite and positive on the way: black.
-template <bool BB>
+// PT (with BB; DESIGN.md §15, RRT_DISK_PROFILE_PAGE_THORNE): q is the Page-Thorne flux of the hole's
+// spin over its peak, q = S(x) pt_norm with x = sqrt(r / M) and
+// S = [(x - x0) - 1.5 s ln(x / x0) - sum_i C_i ln((x - x_i) / (x0 - x_i))] / (x^4 (x^3 - 3 x + 2 s)),
+// the host's constants (rrt_blackbody.cpp rrt_pt_constants): + - x / sqrt and rrt_glibm_log four times.
+// B is exactly 0 at r = r_in (log 1 = 0); below r_in (rrt_disk_eval only: a crossing has r >= r_in)
+// there is no disk: black.
+template <bool BB, bool PT>
 __device__ __forceinline__ spec disk_rgb(const DDisk& dd, double r, double g) {
   const double c = xdiv(dd.r_in, r);
   const double c3 = (c * c) * c;
@@ -1127,7 +1141,16 @@ __device__ __forceinline__ spec disk_rgb(const DDisk& dd, double r, double g) {
     return S(dd.emission[0] * (float)w, dd.emission[1] * (float)w, dd.emission[2] * (float)w);
   }
   double q = c3;
-  if (dd.profile == RRT_DISK_PROFILE_ZERO_TORQUE) q = (c3 * (1.0 - xsqrt(c))) * RRT_BB_F_NORM;
+  if (PT) {
+    const double x = xdiv(xsqrt(r), dd.sqrt_m);
+    if (!(x >= dd.pt_x0)) return S(0, 0, 0);
+    double B = (x - dd.pt_x0) - dd.pt_ca * rrt_glibm_log(xdiv(x, dd.pt_x0));
+#pragma unroll
+    for (int i = 0; i < 3; ++i) B = B - dd.pt_c[i] * rrt_glibm_log(xdiv(x - dd.pt_x[i], dd.pt_d[i]));
+    const double x2 = x * x;
+    const double den = (x2 * x2) * (((x2 * x) - 3.0 * x) + dd.pt_2a);
+    q = xdiv(B, den) * dd.pt_norm;
+  } else if (dd.profile == RRT_DISK_PROFILE_ZERO_TORQUE) q = (c3 * (1.0 - xsqrt(c))) * RRT_BB_F_NORM;
   if (!(q > 0.0)) return S(0, 0, 0);
   const double t = dd.temperature * xsqrt(xsqrt(q));
   const double t_obs = (dd.no_redshift ? 1.0 : g) * t;
@@ -1165,8 +1188,8 @@ __device__ __forceinline__ bool disk_sample(const DHole& h, const DDisk& dd, v3 
 // DISK: with kp.disk.on every step is tested against the accretion disk next to its chord's segment
 // query: a capture wins; else the chord's closest primitive hit wins iff its
 // t <= t_disk = s max_t, else the disk (*dk; the Isect and qr->t as for a hit, bsdf and slot -1).
-// BB: dk->rgb is the blackbody colour.
-template <bool ANY, bool COUNT, bool EXIT, bool DISK, bool BB>
+// BB: dk->rgb is the blackbody colour; PT: with the Page-Thorne profile (§15).
+template <bool ANY, bool COUNT, bool EXIT, bool DISK, bool BB, bool PT>
 __device__ __forceinline__ bool kerr_march(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn, QRec* qr, ExitRec* xr,
                                            DiskRec* dk) {
   const DHole& h = kp.hole;
@@ -1230,7 +1253,7 @@ __device__ __forceinline__ bool kerr_march(const KParams& kp, v3 o, v3 d, Isect*
         if (prim && !(cross && q2->t > t_disk)) return true;
         if (cross) {
           double g;
-          const spec rgb = disk_radiance<BB>(h, kp.disk, x, y, lz, g);
+          const spec rgb = disk_radiance<BB, PT>(h, kp.disk, x, y, lz, g);
           if (dk) { dk->hit = true; dk->rgb = rgb; }
           const double gs = above ? g : -g;
           is->hit_p = a + vmul(sd, t_disk);
@@ -1491,11 +1514,12 @@ __device__ __forceinline__ bool shadow_occluded_proof(const KParams& kp, v3 o, v
 // row -- that row's capture test and walk, and every later row, are not run -- and *xr (if given)
 // says whether and where the ray escaped; Kerr: kerr_march's far march.
 // DISK (Kerr exit-mode builds): the march tests the accretion disk too (kerr_march; *dk); BB: its
-// colour is the blackbody rule's
-template <bool ANY, bool COUNT, bool KERR = false, bool W4 = true, bool EXIT = false, bool DISK = false, bool BB = false>
+// colour is the blackbody rule's; PT: with the Page-Thorne profile
+template <bool ANY, bool COUNT, bool KERR = false, bool W4 = true, bool EXIT = false, bool DISK = false, bool BB = false,
+          bool PT = false>
 RRT_QUERY_ATTR bool query(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn, bool any_rt = false,
                           QRec* qr = nullptr, ExitRec* xr = nullptr, DiskRec* dk = nullptr) {
-  if (KERR && EXIT) return kerr_march<ANY, COUNT, true, DISK, BB>(kp, o, d, is, cn, qr, xr, dk);
+  if (KERR && EXIT) return kerr_march<ANY, COUNT, true, DISK, BB, PT>(kp, o, d, is, cn, qr, xr, dk);
   if (KERR) return qr ? kerr_march<ANY, COUNT>(kp, o, d, is, cn, qr) : query_kerr<ANY, COUNT>(kp, o, d, is, cn);
   if (qr) qr->steps = (uint32_t)kp.hole.steps;  // all marched, unless a segment below ends the march
   if (COUNT && !kp.count_exec && !(kp.diag & 2)) cn.query++;

@@ -1294,7 +1294,8 @@ extern "C" int rrt_set_disk(rrt_ctx* c, const rrt_disk_desc* d) {
   if (d->flags & RRT_DISK_BLACKBODY) {  // DESIGN.md §13; the range keeps every intermediate of the rule finite
     if (!(std::isfinite(d->temperature) && d->temperature >= (float)RRT_BB_T_MIN && d->temperature <= (float)RRT_BB_T_MAX))
       return fail(c, RRT_E_INVALID, "a blackbody disk's temperature must lie in [1000, 1e6] K");
-    if (d->profile != RRT_DISK_PROFILE_POWER && d->profile != RRT_DISK_PROFILE_ZERO_TORQUE)
+    if (d->profile != RRT_DISK_PROFILE_POWER && d->profile != RRT_DISK_PROFILE_ZERO_TORQUE &&
+        d->profile != RRT_DISK_PROFILE_PAGE_THORNE)  // 2 is unassigned
       return fail(c, RRT_E_INVALID, "unknown rrt_disk_desc profile");
   }
   c->disk = *d;
@@ -1343,6 +1344,11 @@ static int fill_disk_params(rrt_ctx* c, KParams& kp) {
     d.profile = c->disk.profile;
     d.temperature = (double)c->disk.temperature;
     rrt_bb_constants(d.temperature, d.bb_k, d.bb_n);
+    if (d.profile == RRT_DISK_PROFILE_PAGE_THORNE) {  // the builds V_KERR_DISK_PT / V_KERR_DISK_PT_LIGHT;
+      // per launch like r_in: the spin may have changed since rrt_set_disk.  x0 as the device forms x at r_in
+      d.pt_x0 = std::sqrt(d.r_in) / d.sqrt_m;
+      rrt_pt_constants(hole_spin(h), d.pt_x0, &d.pt_ca, &d.pt_2a, d.pt_x, d.pt_d, d.pt_c, &d.pt_norm);
+    }
   }
   // the annulus in the Kerr-Schild plane (x^2 + y^2 = r^2 + a^2), for disk_sample;
   // light: the builds V_KERR_DISK_LIGHT / V_KERR_DISK_BB_LIGHT
@@ -1708,7 +1714,9 @@ static int launch(rrt_ctx* c, const rrt_render_params* p, const uint32_t* tiles,
     return fail(c, RRT_E_INVALID, "RRT_RENDER_WAVEFRONT (the path pool kernel) renders max_ray_depth >= 2 "
                                   "Schwarzschild frames without counters or switches, n_lights x ns_area_light < 2048");
   const bool pixel_loop = !path_pool && ((deep && !deep_sample) || (p->flags & RRT_RENDER_PIXEL_LOOP) || sw || sky || disk);
-  const int lean = disk ? (kp.disk.light ? (kp.disk.blackbody ? 10 /* V_KERR_DISK_BB_LIGHT */ : 9 /* V_KERR_DISK_LIGHT */)
+  const bool disk_pt = disk && kp.disk.blackbody && kp.disk.profile == RRT_DISK_PROFILE_PAGE_THORNE;
+  const int lean = disk_pt ? (kp.disk.light ? 12 /* V_KERR_DISK_PT_LIGHT */ : 11 /* V_KERR_DISK_PT */)
+                 : disk ? (kp.disk.light ? (kp.disk.blackbody ? 10 /* V_KERR_DISK_BB_LIGHT */ : 9 /* V_KERR_DISK_LIGHT */)
                                          : (kp.disk.blackbody ? 8 /* V_KERR_DISK_BB */ : 7 /* V_KERR_DISK */))
                  : sky ? (kerr ? 6 /* V_KERR_SKY */ : 5 /* V_SKY */)
                  : kerr ? 3 /* V_KERR */

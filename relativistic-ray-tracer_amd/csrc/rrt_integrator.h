@@ -13,12 +13,13 @@ namespace rrt {
 // ray went if it hit nothing (they only).
 // The disk builds (V_KERR_DISK; V_KERR_DISK_BB, §13: the blackbody colour) run the
 // exit-mode march with the disk test; its far march runs only where xr is given (the lensed sky's rule
-// in force).  dk: a hit that is the disk.  Their _LIGHT builds (§14) trace as their parents.
+// in force).  dk: a hit that is the disk.  Their _LIGHT builds (§14) trace as their parents; the _PT
+// builds (§15) as V_KERR_DISK_BB with the Page-Thorne profile.
 template <bool ANY, bool COUNT, bool DEEP, int LEAN>
 __device__ __forceinline__ bool trace(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn, ExitRec* xr = nullptr,
                                       DiskRec* dk = nullptr) {
   return query<ANY, COUNT, is_kerr_build(LEAN), is_lean(LEAN), is_sky(LEAN) || is_disk(LEAN), is_disk(LEAN),
-               is_disk_bb(LEAN)>(kp, o, d, is, cn, false, nullptr, xr, dk);
+               is_disk_bb(LEAN), is_disk_pt(LEAN)>(kp, o, d, is, cn, false, nullptr, xr, dk);
 }
 // the emission a ray picks up at its hit: the hit primitive's BSDF's, or the disk's radiance
 __device__ __forceinline__ spec hit_emission(const KParams& kp, const Isect& is, const DiskRec& dk) {

@@ -196,6 +196,14 @@ struct DDisk {
   double area;            // PI_D x rho_span: the annulus's coordinate area
   uint32_t light;         // 1: RRT_DISK_LIGHT (rendered by V_KERR_DISK_LIGHT / V_KERR_DISK_BB_LIGHT)
   uint32_t pad;
+  // the Page-Thorne profile (RRT_DISK_PROFILE_PAGE_THORNE; rrt_device.h disk_rgb<true, true>,
+  // rrt_blackbody.cpp rrt_pt_constants): filled for that profile only, with s = a / M
+  double pt_x0;           // x = sqrt(r / M) at r_in, as the device forms it: sqrt(r_in M) / sqrt(M)
+  double pt_ca, pt_2a;    // 1.5 s, 2.0 s
+  double pt_x[3];         // the roots of x^3 - 3 x + 2 s
+  double pt_d[3];         // x0 - x_i
+  double pt_c[3];         // C_i = 3 (x_i - s)^2 / (x_i (x_i - x_j)(x_i - x_k)); not finite: 0
+  double pt_norm;         // 1 / S(x_peak): `temperature` is the peak temperature
 };
 
 #define RRT_MAX_QUEUES 8

@@ -230,6 +230,14 @@ __global__ void rrt_disk_kernel(const DDisk disk, double m, uint64_t n, const do
     rgb[3 * k] = s.r; rgb[3 * k + 1] = s.g; rgb[3 * k + 2] = s.b;
   }
 }
+// ... of a blackbody disk with the Page-Thorne profile (disk_rgb<true, true>): a kernel of
+// its own, so that rrt_disk_kernel stays the code it was
+__global__ void rrt_disk_pt_kernel(const DDisk disk, double m, uint64_t n, const double* r_m, const double* g, float* rgb) {
+  for (uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; k < n; k += (uint64_t)gridDim.x * blockDim.x) {
+    const rrt::spec s = rrt::disk_rgb<true, true>(disk, r_m[k] * m, g[k]);
+    rgb[3 * k] = s.r; rgb[3 * k + 1] = s.g; rgb[3 * k + 2] = s.b;
+  }
+}
 // The disk light's sampler as disk_direct evaluates it (rrt_device.h disk_sample) on n
 // shading points p [n][3] and draws uv [n][2]: rrt_disk_sample, the checker's handle on points and
 // draws no frame reaches (tests/test_gpu_disk_light.py).  An invalid sample: pdf 0.
@@ -267,6 +275,10 @@ hipError_t rrt_launch_render(const KParams& kp, const KParams* d_kp, int deep, i
     RRT_LAUNCH(true, false, rrt::V_KERR_DISK_LIGHT, 2);
   } else if (lean == rrt::V_KERR_DISK_BB_LIGHT) {
     RRT_LAUNCH(true, false, rrt::V_KERR_DISK_BB_LIGHT, 2);
+  } else if (lean == rrt::V_KERR_DISK_PT) {  // builds 8 and 10 with the Page-Thorne profile
+    RRT_LAUNCH(true, false, rrt::V_KERR_DISK_PT, 2);
+  } else if (lean == rrt::V_KERR_DISK_PT_LIGHT) {
+    RRT_LAUNCH(true, false, rrt::V_KERR_DISK_PT_LIGHT, 2);
   } else if (lean == rrt::V_SW) {  // the reference's switches as run-time flags: one bounce-capable build
     if (count) RRT_LAUNCH(true, true, rrt::V_SW, 1); else RRT_LAUNCH(true, false, rrt::V_SW, 1);
   } else if (lean == rrt::V_KERR) {  // the Kerr builds (general integrator)
@@ -337,7 +349,10 @@ hipError_t rrt_launch_disk(const DDisk& disk, double m, uint64_t n, const double
   uint64_t grid = (n + 255) / 256;
   if (grid > 8192) grid = 8192;
   if (grid == 0) grid = 1;
-  hipLaunchKernelGGL(rrt_disk_kernel, dim3((uint32_t)grid), dim3(256), 0, stream, disk, m, n, r_m, g, rgb);
+  if (disk.blackbody && disk.profile == RRT_DISK_PROFILE_PAGE_THORNE)
+    hipLaunchKernelGGL(rrt_disk_pt_kernel, dim3((uint32_t)grid), dim3(256), 0, stream, disk, m, n, r_m, g, rgb);
+  else
+    hipLaunchKernelGGL(rrt_disk_kernel, dim3((uint32_t)grid), dim3(256), 0, stream, disk, m, n, r_m, g, rgb);
   return hipGetLastError();
 }
 hipError_t rrt_launch_disk_sample(const DHole& hole, const DDisk& disk, uint64_t n, const double* p, const double* uv,

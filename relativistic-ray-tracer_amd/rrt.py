@@ -90,7 +90,9 @@ RRT_DISK_NO_REDSHIFT = 1  # rrt_disk_desc.flags
 RRT_DISK_BLACKBODY = 4    # the blackbody disk; bit 1 is unassigned and rejected
 RRT_DISK_LIGHT = 16       # the disk importance-sampled as a light; bit 3 is unassigned and rejected
 RRT_DISK_PROFILE_POWER, RRT_DISK_PROFILE_ZERO_TORQUE = 0, 1  # rrt_disk_desc.profile
-DISK_PROFILES = {"power": RRT_DISK_PROFILE_POWER, "zero-torque": RRT_DISK_PROFILE_ZERO_TORQUE}
+RRT_DISK_PROFILE_PAGE_THORNE = 3  # the Page-Thorne flux of the spin in force; 2 is unassigned and rejected
+DISK_PROFILES = {"power": RRT_DISK_PROFILE_POWER, "zero-torque": RRT_DISK_PROFILE_ZERO_TORQUE,
+                 "page-thorne": RRT_DISK_PROFILE_PAGE_THORNE}
 
 
 class DiskDesc(C.Structure):  # rrt_disk_desc
@@ -485,8 +487,9 @@ class Renderer:
         (in M; r_in=0: the prograde ISCO of the spin in force) of the equatorial plane, radiance
         emission x (r_in / r)^3 x g^4; redshift=False: g = 1.  set_disk(None) removes it.
         temperature (Kelvin, 1000..1e6): the blackbody disk with the temperature profile
-        "power" (T ~ r^-3/4, `temperature` at r_in) or "zero-torque" (`temperature` at its peak,
-        r = 49/36 r_in); emission is then the colour of gas at `temperature` seen at g = 1.
+        "power" (T ~ r^-3/4, `temperature` at r_in), "zero-torque" (`temperature` at its peak,
+        r = 49/36 r_in) or "page-thorne" (T^4 follows the Page-Thorne flux of the spin in
+        force, `temperature` at its peak, the inner edge black); emission is then the colour of gas at `temperature` seen at g = 1.
         emission=None: (1, 1, 1), with a temperature blackbody_tint(temperature).
         light=True (RRT_DISK_LIGHT): importance-sampled direct light samples the disk too,
         ns_area_light points of its flat image, after the listed lights."""
