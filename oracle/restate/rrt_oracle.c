@@ -10,12 +10,17 @@
  * keyed per-pixel generator of oracle/ref/harness_common.h, exactly as in the oracle harness.
  *
  * Pinned by tests/test_oracle_*.py against tests/golden/ (reference-generated).
+ * The build's own spacetime features have no reference and are restated from DESIGN.md and the device
+ * code: the Kerr march (§10; tests/test_kerr_oracle.py) and, behind ro_params' extension fields (0 by default),
+ * the exit mode and lensed sky (§11), the plain accretion disk (§12) and the disk light (§14), pinned
+ * against the numpy checkers by tests/test_disk_oracle.py.
  * Used by: tests/ (checker), __graft_entry__.smoke() (checker), bench.py (cpu_baseline).
  */
 #include "rrt_oracle.h"
 
 #include <math.h>
 #include <pthread.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -329,12 +334,20 @@ int ro_camera_load(const char* path, ro_camera* cam, char* err, int errlen) {
 }
 
 void ro_params_default(ro_params* p) {
-  memset(p, 0, sizeof(*p));
+  /* the base record alone: a caller built against the record as it was before the extension owns no more */
+  memset(p, 0, offsetof(ro_params, lensed_sky));
   p->ns_aa = 1; p->max_ray_depth = 1; p->ns_area_light = 1; p->samples_per_batch = 32;
   p->max_tolerance = 0.05f; p->direct_hemisphere = 0; p->seed = 0;
   p->bh_center[0] = 0; p->bh_center[1] = 1; p->bh_center[2] = 0; p->bh_radius = 0.1; p->bh_dtheta = 0.1;
   p->illum = 2; p->adaptive = 1; p->thin_lens = 0; p->env_hemi = 0; p->microfacet_hemi = 0;  /* ILLUM, ADAPTIVE, ... */
 }
+void ro_params_default_ext(ro_params* p) {
+  memset(p, 0, sizeof(*p));
+  ro_params_default(p);
+  p->ext = RO_PARAMS_EXT;
+}
+/* the extension fields may be read: the caller's record has them */
+static inline int params_ext(const ro_params* p) { return p->ext == RO_PARAMS_EXT; }
 
 /* ------------------------------------------------------------------ rays & geometry */
 typedef struct { v3 o, d; double min_t, max_t; } ray_t;
@@ -451,8 +464,10 @@ static inline int prim_hit(const ro_scene* s, const prim_t* p, ray_t* r, isect_t
   return sphere_hit(p->c, p->r2, r, is, (int)p->bsdf);
 }
 
-/* BlackHole::next_micro_ray (blackhole.cpp:17-40) */
-static inline ray_t next_micro_ray(const hole_t* h, const ray_t* ray) {
+/* the step's orbital-plane state (exit mode): unit x, y, u and u' before the update, v = u after it */
+typedef struct { v3 x, y; double u, up, v; } micro_out;
+/* BlackHole::next_micro_ray (blackhole.cpp:17-40); mo (may be NULL): stores only, no operation changes */
+static inline ray_t next_micro_ray_mo(const hole_t* h, const ray_t* ray, micro_out* mo) {
   ray_t ret;
   ret.o = vadd(ray->o, vmul(ray->d, ray->max_t));
   ret.min_t = 0.0;
@@ -471,7 +486,9 @@ static inline ray_t next_micro_ray(const hole_t* h, const ray_t* ray) {
   double f2 = -u2 + k * u2 * u2 / 2.0;
   double u3 = u + up * dt / 2.0 + f1 * dt * dt / 4.0;
   double f3 = -u3 + k * u3 * u3 / 2.0;
+  if (mo) { mo->x = x_axis; mo->y = y_axis; mo->u = u; mo->up = up; }
   u += up * dt + (f1 + f2 + f3) * dt * dt / 6.0;
+  if (mo) mo->v = u;
   d = 1 / u;
   double next_x = d * h->cos_dt, next_y = d * h->sin_dt;
   ret.d = vsub(vadd(vadd(h->c, smul(next_x, x_axis)), smul(next_y, y_axis)), ret.o);
@@ -479,6 +496,7 @@ static inline ray_t next_micro_ray(const hole_t* h, const ray_t* ray) {
   ret.d = vnormalize(ret.d);
   return ret;
 }
+static inline ray_t next_micro_ray(const hole_t* h, const ray_t* ray) { return next_micro_ray_mo(h, ray, NULL); }
 
 /* ---- Kerr null geodesics (build-defined; restates rrt_device.h kerr_* operation for operation).
  * Kerr-Schild Cartesian coordinates about the hole, spin along the local z:
@@ -583,11 +601,30 @@ static inline int kerr_advance(const hole_t* h, v3* q, v3* p, double* swept) {
   return kerr_advance_st(h, q, p, swept, 1.0);  /* (dt r) * 1 = dt r exactly */
 }
 
+/* The accretion disk's constants (rrt_host.cpp fill_disk_params) */
+typedef struct {
+  int on, no_redshift, light;
+  double r_in, r_in2, r_out2, sqrt_m, k;  /* scene units */
+  double rho_in2, rho_span, area;         /* the annulus in the Kerr-Schild plane (disk_sample) */
+  float em[3];
+} disk_t;
+
 typedef struct {
   const ro_scene* s;
   hole_t hole;
   rng_t* g;
+  int lensed;       /* RRT_SPACETIME_LENSED_SKY: every query the exit-mode march */
+  disk_t disk;      /* disk.on: every query the disk-aware Kerr march */
+  uint32_t* ev;     /* the pixel's event counts (ro_render_events), or NULL */
 } qctx;
+
+/* What a query of the exit-mode / disk-aware marches reports beyond the Isect (rrt_device.h QRec,
+ * ExitRec, DiskRec) */
+typedef struct {
+  uint32_t steps; int captured; double t;
+  int escaped; v3 e;
+  int disk; spec rgb;
+} qrec_t;
 
 /* BVHAccel::intersect_micro (bvh.cpp:115-138): recursive, left then right, no early exit */
 static int intersect_micro(qctx* q, ray_t* r, isect_t* is, int node) {
@@ -644,6 +681,240 @@ static int bvh_intersect(qctx* q, v3 o, v3 d, isect_t* is) {
     if (intersect_micro(q, &micro, is, 0)) return 1;
   }
   return 0;
+}
+
+/* ------------------------------------------------------------------ the build's own marches
+ * Exit mode and the accretion disk (§12), restated from rrt_device.h operation for
+ * operation: query with EXIT and exit_dir, kerr_march with EXIT / DISK, kerr_far_march, disk_cross,
+ * disk_radiance and the plain disk_rgb.  No reference: pinned against the numpy checkers
+ * (tests/exit_check.py, tests/disk_check.py) by tests/test_disk_oracle.py. */
+#define RO_SKY_FAR_M 1000.0 /* include/rrt.h RRT_SKY_FAR_M */
+
+/* the asymptote of the escape row: e = (-u' x + u y) / |(u, u')|; escaped iff u, u' finite and u' < 0 */
+static inline void exit_dir(const micro_out* mo, qrec_t* r) {
+  const double u = mo->u, up = mo->up;
+  const double s = sqrt(u * u + up * up);
+  const double cx = (-up) / s, cy = u / s;
+  r->e = V(cx * mo->x.x + cy * mo->y.x, cx * mo->x.y + cy * mo->y.y, cx * mo->x.z + cy * mo->y.z);
+  r->escaped = isfinite(u) && isfinite(up) && up < 0.0;
+}
+
+/* the Schwarzschild march with a record; exit: it stops at the escape row (the first whose updated u is
+ * not > 0, NaN included) before that row's capture test and walk */
+static int bvh_intersect_rec(qctx* q, v3 o, v3 d, isect_t* is, int exit, qrec_t* r) {
+  ray_t micro; micro.o = o; micro.d = d; micro.min_t = 0.0; micro.max_t = 0.0;
+  q->g->queries++;
+  r->steps = (uint32_t)q->hole.steps;  /* all marched, unless a row below ends the march */
+  for (int j = 0; j < q->hole.steps; ++j) {
+    micro_out mo;
+    micro = next_micro_ray_mo(&q->hole, &micro, &mo);
+    q->g->micro_steps++;
+    if (exit && !(mo.v > 0.0)) {
+      r->steps = (uint32_t)j + 1u;
+      exit_dir(&mo, r);
+      return 0;
+    }
+    ray_t probe = micro;
+    if (sphere_hit(q->hole.c, q->hole.r2, &probe, NULL, -1)) {
+      r->steps = (uint32_t)j + 1u; r->captured = 1;
+      return 0;
+    }
+    if (intersect_micro(q, &micro, is, 0)) {
+      r->steps = (uint32_t)j + 1u; r->t = micro.max_t;
+      return 1;
+    }
+  }
+  return 0;
+}
+
+/* a step of the far march: the march's own step without the escape test and the swept angle */
+static inline void kerr_advance_far(const hole_t* h, v3* q, v3* p) {
+  v3 dq1, dp1;
+  double r;
+  kerr_rhs(h, *q, *p, &dq1, &dp1, &r);
+  const double hh = ((h->dt * r) * 1.0) / vnorm(dq1);
+  kerr_step(h, q, p, dq1, dp1, hh);
+}
+/* The far march: from the state (q, p) the march escaped at, a the last segment's end (the ray's origin
+ * if no step was taken), on with the march's steps until one ends beyond RO_SKY_FAR_M x M: that step's
+ * unit chord is the exit direction.  A fresh budget of kerr_max_steps; running out: not escaped. */
+static void kerr_far_march(const hole_t* h, v3 q, v3 p, v3 a, qrec_t* r) {
+  const double far = RO_SKY_FAR_M * h->m, far2 = far * far;
+  for (int j = 0; j < h->kerr_max_steps; ++j) {
+    v3 q1 = q, p1 = p;
+    kerr_advance_far(h, &q1, &p1);
+    if (vnorm2(q1) > far2) {
+      const v3 seg = vsub(kerr_world(h, q1), j == 0 ? a : kerr_world(h, q));
+      const double inv = 1. / vnorm(seg);
+      r->e = V(seg.x * inv, seg.y * inv, seg.z * inv);
+      r->escaped = 1;
+      return;
+    }
+    q = q1; p = p1;
+  }
+}
+
+/* a step (q0 -> q1) crosses the plane z = 0 iff z changes sign or ends on it, at the fraction s; true iff
+ * the linearly interpolated point lies on the annulus r_in2 <= x^2 + y^2 - a^2 <= r_out2 */
+static inline int disk_cross(const hole_t* h, const disk_t* dd, v3 q0, v3 q1, double* s, double* x, double* y) {
+  if (!((q0.z > 0.0 && q1.z <= 0.0) || (q0.z < 0.0 && q1.z >= 0.0))) return 0;
+  *s = q0.z / (q0.z - q1.z);
+  *x = q0.x + *s * (q1.x - q0.x);
+  *y = q0.y + *s * (q1.y - q0.y);
+  const double r2 = (*x * *x + *y * *y) - h->a2;
+  return r2 >= dd->r_in2 && r2 <= dd->r_out2;
+}
+/* redshift g = 1 / (u^t (1 - Omega L_z)) of the prograde circular orbit at the crossing, and the plain
+ * colour emission x (float)((r_in / r)^3 g^4) */
+static inline spec disk_radiance(const hole_t* h, const disk_t* dd, double x, double y, double lz, double* g_out) {
+  const double r = sqrt((x * x + y * y) - h->a2);
+  double g = 1.0;
+  if (!dd->no_redshift) {
+    const double r32 = r * sqrt(r);
+    const double kr = dd->k / r32;
+    const double om = dd->sqrt_m / (r32 + dd->k);
+    const double ut = (1.0 + kr) / sqrt((1.0 - (3.0 * h->m) / r) + 2.0 * kr);
+    g = 1.0 / (ut * (1.0 - om * lz));
+    if (!(g > 0.0 && isfinite(g))) g = 0.0;
+  }
+  *g_out = g;
+  const double c = dd->r_in / r;
+  double w = (c * c) * c;
+  if (!dd->no_redshift) {
+    const double g2 = g * g;
+    w = w * (g2 * g2);
+  }
+  return S(dd->em[0] * (float)w, dd->em[1] * (float)w, dd->em[2] * (float)w);
+}
+
+/* The Kerr march with a record.  far: an escaping photon goes on to its exit direction.  With the disk
+ * every step is tested against it next to its chord's walk: a capture wins; else the chord's closest
+ * primitive hit wins iff its t <= t_disk = s max_t, else the disk.  any: a shadow query -- a crossing
+ * occludes; rec: its status is the closest-hit query's (the ray queries). */
+static int kerr_march_rec(qctx* q, v3 o, v3 d, isect_t* is, int any, int rec, int far, qrec_t* r) {
+  const hole_t* h = &q->hole;
+  const disk_t* dd = &q->disk;
+  v3 kq, kp;
+  kerr_init(h, o, d, &kq, &kp);
+  v3 a = o;
+  const double rh2 = h->r_hor * h->r_hor;
+  double swept = 0.0;
+  q->g->queries++;
+  for (int j = 0; j < h->kerr_max_steps && swept < 2.0 * PI_D; ++j) {
+    const v3 q0 = kq, p0 = kp;
+    r->steps = (uint32_t)j + 1u;  /* the step being taken: the one that escapes, captures or hits */
+    if (kerr_advance(h, &kq, &kp, &swept)) {  /* escaped: (kq, kp) untouched */
+      if (far) kerr_far_march(h, kq, kp, a, r);
+      return 0;
+    }
+    q->g->micro_steps++;
+    if (kerr_r2(h, kq) <= rh2) { r->captured = 1; return 0; }
+    const v3 b = kerr_world(h, kq);
+    ray_t micro;
+    micro.o = a; micro.d = vsub(b, a); micro.min_t = 0.0;
+    micro.max_t = vnorm(micro.d);
+    micro.d = vnormalize(micro.d);
+    if (dd->on) {
+      double s = 0.0, x = 0.0, y = 0.0;
+      const int cross = disk_cross(h, dd, q0, kq, &s, &x, &y);
+      const double t_disk = s * micro.max_t;
+      /* the interpolated covector's L_z = x p_y - y p_x */
+      const double lz = x * (p0.y + s * (kp.y - p0.y)) - y * (p0.x + s * (kp.x - p0.x));
+      const int above = q0.z > 0.0;
+      if (any) {
+        if (cross) {
+          r->disk = 1;
+          if (!rec) return 1;  /* a shadow ray is occluded by either */
+          isect_t li; ray_t walk = micro;
+          if (intersect_micro(q, &walk, &li, 0) && walk.max_t <= t_disk) r->disk = 0;
+          return 1;
+        }
+        if (intersect_micro(q, &micro, NULL, 0)) return 1;
+      } else {
+        const v3 sd = micro.d;
+        const int prim = intersect_micro(q, &micro, is, 0);  /* a hit leaves its t in micro.max_t */
+        if (prim && !(cross && micro.max_t > t_disk)) { r->t = micro.max_t; return 1; }
+        if (cross) {
+          double g;
+          r->rgb = disk_radiance(h, dd, x, y, lz, &g);
+          r->disk = 1;
+          const double gs = above ? g : -g;
+          is->hit_p = vadd(a, vmul(sd, t_disk));
+          is->w_out = vneg(sd);
+          is->n = V(h->ez.x * gs, h->ez.y * gs, h->ez.z * gs);
+          is->bsdf = -1;
+          r->t = t_disk;
+          return 1;
+        }
+      }
+    } else if (intersect_micro(q, &micro, any ? NULL : is, 0)) {
+      r->t = micro.max_t;
+      return 1;
+    }
+    a = b;
+  }
+  return 0;
+}
+
+/* The integrator's query: the reference's march (bvh_intersect, untouched) unless the lensed sky or the
+ * disk is in force.  far: the caller wants the exit direction (Kerr: the far march runs for it alone;
+ * the Schwarzschild exit-mode march knows it anyway). */
+static int trace_q(qctx* q, v3 o, v3 d, isect_t* is, int any, int far, qrec_t* r) {
+  memset(r, 0, sizeof(*r));
+  if (q->hole.kerr) {
+    if (q->disk.on || q->lensed) {
+      isect_t tmp;
+      return kerr_march_rec(q, o, d, any ? NULL : (is ? is : &tmp), any, 0, far, r);
+    }
+  } else if (q->lensed) {
+    return bvh_intersect_rec(q, o, d, any ? NULL : is, 1, r);
+  }
+  return bvh_intersect(q, o, d, any ? NULL : is);
+}
+
+/* the disk's constants from the params (rrt_host.cpp fill_disk_params), the escape radius widened to
+ * hold it; call with the hole set.  -2: a disk the host rejects. */
+static int disk_init(qctx* q, const ro_params* p) {
+  memset(&q->disk, 0, sizeof(q->disk));
+  q->lensed = params_ext(p) && p->lensed_sky != 0;
+  q->ev = NULL;
+  if (!params_ext(p) || !p->disk_on) return 0;
+  if (!q->hole.kerr || !(p->disk_r_out > p->disk_r_in)) return -2;
+  hole_t* h = &q->hole;
+  disk_t* d = &q->disk;
+  d->r_in = p->disk_r_in * h->m;
+  d->r_in2 = d->r_in * d->r_in;
+  const double r_out = p->disk_r_out * h->m;
+  d->r_out2 = r_out * r_out;
+  d->sqrt_m = sqrt(h->m);
+  d->k = h->a * d->sqrt_m;
+  for (int k = 0; k < 3; ++k) d->em[k] = p->disk_emission[k];
+  d->on = 1;
+  d->no_redshift = (p->disk_flags & RO_DISK_NO_REDSHIFT) ? 1 : 0;
+  d->rho_in2 = d->r_in2 + h->a2;
+  d->rho_span = d->r_out2 - d->r_in2;
+  d->area = PI_D * d->rho_span;
+  d->light = (p->disk_flags & RO_DISK_LIGHT) ? 1 : 0;
+  const double e2 = d->r_out2 + h->a2;  /* |q|^2 on the plane at r_out */
+  if (e2 > h->r_esc2) h->r_esc2 = e2;
+  return 0;
+}
+
+/* The disk as a light (rrt_device.h disk_sample): a point of the annulus uniform in the
+ * coordinate area of the Kerr-Schild plane, the flat direction to it and the flat solid-angle density. */
+static inline int disk_sample(const hole_t* h, const disk_t* dd, v3 p, double u, double v, v3* wi, float* pdf) {
+  const double rho = sqrt(dd->rho_in2 + u * dd->rho_span);
+  const double phi = (2.0 * PI_D) * v;
+  const double x = rho * cos(phi);
+  const double y = rho * sin(phi);
+  const v3 P = kerr_world(h, V(x, y, 0.0));
+  const v3 dv = vsub(P, p);
+  const double d2 = vnorm2(dv);
+  const double inv = 1.0 / sqrt(d2);
+  *wi = V(dv.x * inv, dv.y * inv, dv.z * inv);
+  const double c = fabs(vdot(*wi, h->ez));
+  *pdf = (float)(d2 / (dd->area * c));
+  return isfinite(*pdf) && *pdf > 0.0f;
 }
 
 /* ------------------------------------------------------------------ BSDFs */
@@ -911,6 +1182,12 @@ typedef struct {
   double lens_r, focal;  /* Camera::lensRadius / focalDistance (thin lens) */
 } pctx;
 
+#define EV(c, k) do { if ((c)->q.ev) (c)->q.ev[k]++; } while (0)
+/* the emission a ray picks up at its hit: the hit primitive's BSDF's, or the disk's radiance */
+static inline spec hit_emission(const pctx* c, const isect_t* is, const qrec_t* r) {
+  return r->disk ? r->rgb : bsdf_emission(&c->q.s->bsdfs[is->bsdf]);
+}
+
 static spec direct_hemisphere(pctx* c, const isect_t* is) { /* :15-31 */
   v3 X, Y, Z; coord_space(is->n, &X, &Y, &Z);
   v3 hit_p = is->hit_p, w_out = to_local(X, Y, Z, is->w_out);
@@ -920,9 +1197,11 @@ static spec direct_hemisphere(pctx* c, const isect_t* is) { /* :15-31 */
   for (int i = 0; i < num; ++i) {
     v3 w_in = hemisphere_sample(c->q.g);
     v3 wi_world = to_world(X, Y, Z, w_in);
-    isect_t is2;
-    if (bvh_intersect(&c->q, vadd(hit_p, smul(EPS_D, wi_world)), wi_world, &is2))
-      L = sadd(L, smulf(smulS(bsdf_emission(&c->q.s->bsdfs[is2.bsdf]), bsdf_f(b, w_out, w_in)), (float)w_in.z));
+    isect_t is2; qrec_t r;
+    if (trace_q(&c->q, vadd(hit_p, smul(EPS_D, wi_world)), wi_world, &is2, 0, 0, &r)) {
+      if (r.disk) EV(c, 2);
+      L = sadd(L, smulf(smulS(hit_emission(c, &is2, &r), bsdf_f(b, w_out, w_in)), (float)w_in.z));
+    }
   }
   return sdivf(smulf(smulf(L, 2.0f), (float)M_PI), (float)num);
 }
@@ -942,14 +1221,57 @@ static spec direct_importance(pctx* c, const isect_t* is) { /* :33-57 */
       spec sample = light_sample_L_sw(c->q.s, l, c->q.g, hit_p, &wi_world, &dist, &pdf, (int)c->p->env_hemi);
       v3 w_in = to_local(X, Y, Z, wi_world);
       if (w_in.z < 0) continue;
-      if (!bvh_intersect(&c->q, vadd(hit_p, smul(EPS_D, wi_world)), wi_world, NULL))
+      qrec_t r;
+      if (c->q.lensed && l->type == 5) {
+        /* lensed sky: the environment light's sample counts iff its shadow ray escapes,
+         * with the map's radiance along the exit direction; wi, pdf, the BSDF term and the draws stay */
+        if (trace_q(&c->q, vadd(hit_p, smul(EPS_D, wi_world)), wi_world, NULL, 1, 1, &r)) {
+          if (r.disk) EV(c, 1);
+          continue;
+        }
+        if (!r.escaped) continue;
+        EV(c, 6);
+        L = sadd(L, sdivf(smulf(smulS(env_dir(c->q.s, r.e), bsdf_f(b, w_out, w_in)), (float)w_in.z), pdf));
+        continue;
+      }
+      if (!trace_q(&c->q, vadd(hit_p, smul(EPS_D, wi_world)), wi_world, NULL, 1, 0, &r))
         L = sadd(L, sdivf(smulf(smulS(sample, bsdf_f(b, w_out, w_in)), (float)w_in.z), pdf));
+      else if (r.disk) EV(c, 1);
     }
   }
   return sdivf(L, (float)total);
 }
 
+/* The disk importance-sampled as a light (rrt_integrator.h disk_direct): ns_area_light
+ * samples of disk_sample, two draws each, each evaluated by the closest-hit march along the bent ray --
+ * the disk's radiance where that ray really ends on it, nothing otherwise -- normalised by their count. */
+static spec disk_direct(pctx* c, const isect_t* is) {
+  v3 X, Y, Z; coord_space(is->n, &X, &Y, &Z);
+  v3 hit_p = is->hit_p, w_out = to_local(X, Y, Z, is->w_out);
+  const bsdf_t* b = &c->q.s->bsdfs[is->bsdf];
+  spec L = S(0, 0, 0);
+  const int num = (int)c->p->ns_area_light;
+  if (num == 0) return L;
+  for (int i = 0; i < num; ++i) {
+    double u, v;
+    grid_sample(c->q.g, &u, &v);
+    v3 wi_world; float pdf;
+    if (!disk_sample(&c->q.hole, &c->q.disk, hit_p, u, v, &wi_world, &pdf)) continue;
+    v3 w_in = to_local(X, Y, Z, wi_world);
+    if (w_in.z < 0) continue;
+    isect_t is2; qrec_t r;
+    if (!trace_q(&c->q, vadd(hit_p, smul(EPS_D, wi_world)), wi_world, &is2, 0, 0, &r) || !r.disk) continue;
+    EV(c, 5);
+    L = sadd(L, sdivf(smulf(smulS(r.rgb, bsdf_f(b, w_out, w_in)), (float)w_in.z), pdf));
+  }
+  return sdivf(L, (float)num);
+}
+
 static spec one_bounce(pctx* c, const isect_t* is) { /* :63-67 */
+  if (c->q.disk.on && c->q.disk.light && !c->p->direct_hemisphere) {
+    const spec Ll = direct_importance(c, is);  /* the listed lights first: their draws */
+    return sadd(Ll, disk_direct(c, is));
+  }
   return c->p->direct_hemisphere ? direct_hemisphere(c, is) : direct_importance(c, is);
 }
 
@@ -966,10 +1288,12 @@ static spec at_least_one_bounce(pctx* c, uint32_t depth, const isect_t* is) { /*
     spec sample = bsdf_sample_f_sw(b, c->q.g, w_out, &w_in, &pdf, (int)c->p->microfacet_hemi);
     if (pdf == 0.0f) return L_out;
     v3 wi_world = to_world(X, Y, Z, w_in);
-    isect_t is2;
-    if (bvh_intersect(&c->q, vadd(hit_p, smul(EPS_D, wi_world)), wi_world, &is2)) {
-      spec L = at_least_one_bounce(c, depth - 1, &is2);
-      if (bsdf_is_delta(b)) L = sadd(L, bsdf_emission(&c->q.s->bsdfs[is2.bsdf]));
+    isect_t is2; qrec_t r;
+    if (trace_q(&c->q, vadd(hit_p, smul(EPS_D, wi_world)), wi_world, &is2, 0, 0, &r)) {
+      /* a bounce ray that ends on the disk ends the path there: the disk reflects nothing */
+      if (r.disk) EV(c, bsdf_is_delta(b) ? 3 : 4);
+      spec L = r.disk ? S(0, 0, 0) : at_least_one_bounce(c, depth - 1, &is2);
+      if (bsdf_is_delta(b)) L = sadd(L, hit_emission(c, &is2, &r));
       L_out = sadd(L_out, sdivf(sdivf(smulf(smulS(L, sample), (float)fabs(w_in.z)), pdf), (float)prob));
     }
   }
@@ -978,7 +1302,25 @@ static spec at_least_one_bounce(pctx* c, uint32_t depth, const isect_t* is) { /*
 
 static spec est_radiance(pctx* c, v3 o, v3 d) { /* :103-123, ILLUM == 2 */
   isect_t is;
-  if (!bvh_intersect(&c->q, o, d, &is)) /* miss: envLight->sample_dir(r), r unbent */
+  if (c->q.disk.on) {
+    /* the disk: a camera ray that reaches it returns its radiance; a miss takes the sky
+     * rule in force -- the lensed sky's (the far march runs) or the reference's (it does not) */
+    qrec_t r;
+    if (!trace_q(&c->q, o, d, &is, 0, c->q.lensed, &r)) {
+      if (r.escaped) EV(c, 7);
+      if (!c->q.s->env_w) return S(0, 0, 0);
+      if (!c->q.lensed) return env_dir(c->q.s, d);
+      return r.escaped ? env_dir(c->q.s, r.e) : S(0, 0, 0);
+    }
+    if (r.disk) { EV(c, 0); return r.rgb; }
+  } else if (c->q.lensed) {
+    /* lensed sky: the map along an escaping ray's exit direction; the hole's shadow is black */
+    qrec_t r;
+    if (!trace_q(&c->q, o, d, &is, 0, 1, &r)) {
+      if (r.escaped) EV(c, 7);
+      return (r.escaped && c->q.s->env_w) ? env_dir(c->q.s, r.e) : S(0, 0, 0);
+    }
+  } else if (!bvh_intersect(&c->q, o, d, &is)) /* miss: envLight->sample_dir(r), r unbent */
     return c->q.s->env_w ? env_dir(c->q.s, d) : S(0, 0, 0);
   if (c->p->illum == 0) /* normal_shading (pathtracer.h:199-201) */
     return sadd(smulf(S((float)is.n.x, (float)is.n.y, (float)is.n.z), (float).5), S(.5f, .5f, .5f));
@@ -1045,6 +1387,7 @@ static void pctx_init(pctx* c, const ro_scene* s, const ro_camera* cam, const ro
     hole_init_kerr(&c->q.hole, p->bh_center, p->bh_radius, p->bh_dtheta, p->bh_spin, p->bh_axis);
     kerr_set_escape(&c->q.hole, s->nodes[0].mn, s->nodes[0].mx);
   } else hole_init(&c->q.hole, p->bh_center, p->bh_radius, p->bh_dtheta);
+  disk_init(&c->q, p);  /* ro_render has checked it */
   c->cam_pos = V(cam->pos[0], cam->pos[1], cam->pos[2]);
   c->c2w0 = V(cam->c2w[0], cam->c2w[3], cam->c2w[6]);
   c->c2w1 = V(cam->c2w[1], cam->c2w[4], cam->c2w[7]);
@@ -1059,7 +1402,7 @@ static void pctx_init(pctx* c, const ro_scene* s, const ro_camera* cam, const ro
 typedef struct {
   const ro_scene* s; const ro_camera* cam; const ro_params* p;
   uint32_t x0, y0, w, h, tiles_w, ntiles;
-  float* rgb; int32_t* count; uint32_t* draws; uint32_t* counters;
+  float* rgb; int32_t* count; uint32_t* draws; uint32_t* counters; uint32_t* events;
   int next; pthread_mutex_t mu;
 } job_t;
 
@@ -1067,6 +1410,8 @@ static void* worker(void* arg) {
   job_t* j = (job_t*)arg;
   rng_t g; memset(&g, 0, sizeof(g));
   pctx c; pctx_init(&c, j->s, j->cam, j->p, &g);
+  uint32_t ev[RO_EV_N];
+  if (j->events) c.q.ev = ev;
   for (;;) {
     pthread_mutex_lock(&j->mu);
     int t = j->next++;
@@ -1079,8 +1424,10 @@ static void* worker(void* arg) {
         g.key = ro_pixel_key(j->p->seed, px, py); g.ctr = 0;
         g.bbox_tests = g.micro_steps = g.prim_tests = g.queries = 0;
         int32_t cnt;
+        memset(ev, 0, sizeof(ev));
         spec s = raytrace_pixel(&c, px, py, &cnt);
         size_t k = (size_t)yy * j->w + xx;
+        if (j->events) memcpy(j->events + RO_EV_N * k, ev, sizeof(ev));
         j->rgb[3 * k] = s.r; j->rgb[3 * k + 1] = s.g; j->rgb[3 * k + 2] = s.b;
         j->count[k] = cnt;
         if (j->draws) j->draws[k] = g.ctr;
@@ -1093,14 +1440,17 @@ static void* worker(void* arg) {
   return NULL;
 }
 
-int ro_render(const ro_scene* s, const ro_camera* cam, const ro_params* p, uint32_t x0, uint32_t y0, uint32_t w,
-              uint32_t h, float* rgb, int32_t* count, uint32_t* draws, uint32_t* counters, int nthreads) {
+static int render_job(const ro_scene* s, const ro_camera* cam, const ro_params* p, uint32_t x0, uint32_t y0, uint32_t w,
+                      uint32_t h, float* rgb, int32_t* count, uint32_t* draws, uint32_t* counters, uint32_t* events,
+                      int nthreads) {
   if (!s || !cam || !p || !rgb || !count || p->frame_w == 0 || p->frame_h == 0 || p->samples_per_batch == 0) return -1;
+  /* a disk needs the Kerr march (the Schwarzschild stepper carries no photon momentum) and r_out > r_in */
+  if (params_ext(p) && p->disk_on && (p->bh_kind != 1 || !(p->disk_r_out > p->disk_r_in))) return -2;
   job_t j;
   memset(&j, 0, sizeof(j));
   j.s = s; j.cam = cam; j.p = p; j.x0 = x0; j.y0 = y0; j.w = w; j.h = h;
   j.tiles_w = (w + 31) / 32; j.ntiles = j.tiles_w * ((h + 31) / 32);
-  j.rgb = rgb; j.count = count; j.draws = draws; j.counters = counters;
+  j.rgb = rgb; j.count = count; j.draws = draws; j.counters = counters; j.events = events;
   pthread_mutex_init(&j.mu, NULL);
   if (nthreads < 1) nthreads = 1;
   pthread_t* th = (pthread_t*)malloc(sizeof(pthread_t) * (size_t)nthreads);
@@ -1109,6 +1459,47 @@ int ro_render(const ro_scene* s, const ro_camera* cam, const ro_params* p, uint3
   free(th);
   pthread_mutex_destroy(&j.mu);
   return 0;
+}
+int ro_render(const ro_scene* s, const ro_camera* cam, const ro_params* p, uint32_t x0, uint32_t y0, uint32_t w,
+              uint32_t h, float* rgb, int32_t* count, uint32_t* draws, uint32_t* counters, int nthreads) {
+  return render_job(s, cam, p, x0, y0, w, h, rgb, count, draws, counters, NULL, nthreads);
+}
+int ro_render_events(const ro_scene* s, const ro_camera* cam, const ro_params* p, uint32_t x0, uint32_t y0, uint32_t w,
+                     uint32_t h, float* rgb, int32_t* count, uint32_t* draws, uint32_t* events, int nthreads) {
+  return render_job(s, cam, p, x0, y0, w, h, rgb, count, draws, NULL, events, nthreads);
+}
+
+int ro_ray_query(const ro_scene* s, const ro_params* p, const double* o, const double* d, int any_hit, double* out) {
+  rng_t g; memset(&g, 0, sizeof(g));
+  qctx q; memset(&q, 0, sizeof(q));
+  q.s = s; q.g = &g;
+  if (p->bh_kind == 1) {
+    hole_init_kerr(&q.hole, p->bh_center, p->bh_radius, p->bh_dtheta, p->bh_spin, p->bh_axis);
+    kerr_set_escape(&q.hole, s->nodes[0].mn, s->nodes[0].mx);
+  } else hole_init(&q.hole, p->bh_center, p->bh_radius, p->bh_dtheta);
+  memset(out, 0, 15 * sizeof(double));
+  out[14] = -1;
+  if (disk_init(&q, p) != 0) return -2;
+  isect_t is; memset(&is, 0, sizeof(is));
+  qrec_t r; memset(&r, 0, sizeof(r));
+  const v3 ov = V(o[0], o[1], o[2]), dv = V(d[0], d[1], d[2]);
+  const int hit = q.hole.kerr ? kerr_march_rec(&q, ov, dv, any_hit ? NULL : &is, any_hit, 1, q.lensed, &r)
+                              : bvh_intersect_rec(&q, ov, dv, any_hit ? NULL : &is, q.lensed, &r);
+  out[0] = r.steps;
+  if (!hit) {
+    if (r.captured) return RO_RAY_CAPTURED;
+    if (!r.escaped) return RO_RAY_MISS;
+    out[11] = r.e.x; out[12] = r.e.y; out[13] = r.e.z;
+    return RO_RAY_ESCAPED;
+  }
+  if (!any_hit) {
+    out[1] = r.t;
+    out[2] = is.hit_p.x; out[3] = is.hit_p.y; out[4] = is.hit_p.z;
+    out[5] = is.n.x; out[6] = is.n.y; out[7] = is.n.z;
+    out[14] = is.bsdf;
+    if (r.disk) { out[8] = r.rgb.r; out[9] = r.rgb.g; out[10] = r.rgb.b; }
+  }
+  return r.disk ? RO_RAY_DISK : RO_RAY_HIT;
 }
 
 /* ------------------------------------------------------------------ KAT entry points */

@@ -55,9 +55,28 @@ typedef struct {
   double bh_spin, bh_axis[3];
   /* the reference's compile-time switches, defaults as the reference build (pathtracer.h:4-6,
    * environment_light.h:4, bsdf.h:4) */
-  uint32_t illum, adaptive, thin_lens, env_hemi, microfacet_hemi, pad2_;
+  /* ext (a padding word of the base record, 0 there): RO_PARAMS_EXT says that the caller's record has
+   * the extension fields below.  A caller built against the base record -- it ends here -- leaves it 0,
+   * and no entry point reads or writes beyond this word then. */
+  uint32_t illum, adaptive, thin_lens, env_hemi, microfacet_hemi, ext;
+  /* ---- extension (read only with ext == RO_PARAMS_EXT) ----
+   * the build's own spacetime features (no reference), restated from DESIGN.md
+   * and the device code and pinned against the numpy checkers by tests/test_disk_oracle.py.  All zero
+   * (ro_params_default_ext): every entry point computes what it computed without them.
+   * lensed_sky: RRT_SPACETIME_LENSED_SKY.  disk_on: the plain accretion disk of rrt_set_disk (Kerr
+   * only), disk_flags RO_DISK_*, disk_r_in / disk_r_out in M (r_in resolved: the caller passes the ISCO),
+   * disk_emission as rrt_disk_desc's.  The blackbody colours (§13, §15) are not restated. */
+  uint32_t lensed_sky, disk_on, disk_flags, pad3_;
+  double disk_r_in, disk_r_out;
+  float disk_emission[3], pad4_;
 } ro_params;
+enum { RO_DISK_NO_REDSHIFT = 1u << 0, RO_DISK_LIGHT = 1u << 4 };  /* RRT_DISK_NO_REDSHIFT, RRT_DISK_LIGHT */
+enum { RO_PARAMS_EXT = 0x524f5831u };  /* "ROX1" */
+/* ro_params_default fills the base record (up to and including ext = 0) and touches nothing beyond it:
+ * callers built against the base record own no more.  ro_params_default_ext fills the whole record:
+ * the base defaults, the extension zeroed, ext = RO_PARAMS_EXT. */
 void ro_params_default(ro_params* p);
+void ro_params_default_ext(ro_params* p);
 
 /* Render region [x0,x0+w) x [y0,y0+h) of the frame (y = 0 at the bottom, sampleBuffer rows).
  * Outputs are row-major over the region.  draws / counters may be NULL.
@@ -66,6 +85,27 @@ void ro_params_default(ro_params* p);
 int ro_render(const ro_scene* s, const ro_camera* cam, const ro_params* p, uint32_t x0, uint32_t y0,
               uint32_t w, uint32_t h, float* rgb, int32_t* count, uint32_t* draws, uint32_t* counters,
               int nthreads);
+
+/* ro_render that also fills per-pixel event counts, events [h][w][RO_EV_N] (may be NULL), summed over
+ * the pixel's samples -- what the frame's paths met (tests/test_gpu_deep_builds.py's floors):
+ * [0] camera rays ending on the disk, [1] listed-light shadow rays occluded at a disk crossing,
+ * [2] hemisphere samples ending on the disk, [3] / [4] bounce rays ending on the disk from a delta / a
+ * non-delta level, [5] disk-light samples that contributed, [6] environment-light shadow rays that
+ * escaped and contributed (lensed sky), [7] escaped camera rays (lensed sky).
+ * Both renders return -2 for a disk under a Schwarzschild-kind hole or with r_out <= r_in. */
+enum { RO_EV_N = 8 };
+int ro_render_events(const ro_scene* s, const ro_camera* cam, const ro_params* p, uint32_t x0, uint32_t y0,
+                     uint32_t w, uint32_t h, float* rgb, int32_t* count, uint32_t* draws, uint32_t* events,
+                     int nthreads);
+
+/* One ray's query under the params in force (lensed_sky: the exit-mode march; disk_on: the disk test),
+ * closest-hit or any-hit -- rrt_trace_rays' record.  Returns the status (RO_RAY_*, include/rrt.h's
+ * RRT_RAY_*) and fills out[15]: [0] steps, [1] t, [2..4] hit_p, [5..7] n, [8..10] the disk's rgb (a
+ * closest-hit DISK record), [11..13] the exit direction (ESCAPED), [14] bsdf.  An any-hit record has
+ * status, steps and the exit direction alone. */
+enum { RO_RAY_MISS = 0, RO_RAY_HIT = 1, RO_RAY_CAPTURED = 2, RO_RAY_ESCAPED = 3, RO_RAY_DISK = 4 };
+int ro_ray_query(const ro_scene* s, const ro_params* p, const double* o, const double* d, int any_hit,
+                 double* out /*15*/);
 
 /* ---- function-level entry points for the known-answer tests ---- */
 /* keyed RNG (oracle/ref/harness_common.h) */

@@ -86,6 +86,12 @@ __device__ __forceinline__ spec raytrace_pixel(const KParams& kp, uint32_t x, ui
     s1 += il;
     s2 += il * il;
     n = i + 1;
+    // The opt-in builds (lensed sky, disk): n must be the lane's own value.  i is the same in every lane
+    // that is still in the loop; in V_KERR_DISK_LIGHT a lane that broke below while others went on
+    // reported a later n after the loop -- count came out as ns_aa and rgb divided by it, the draws
+    // right (tests/test_gpu_deep_builds.py).  Passing n through a vector register here
+    // makes it per-lane; a constant-false condition in every other build.
+    if (is_sky(LEAN) || is_disk(LEAN)) asm volatile("" : "+v"(n));
     if ((uint32_t)n % kp.samples_per_batch == 0) {
       double avg = s1 / n, sd = sqrt((s2 - avg * s1) / i);
       if (1.96 * sd / sqrt((double)n) <= (double)kp.max_tolerance * avg) break;

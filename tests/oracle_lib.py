@@ -33,7 +33,18 @@ class Params(C.Structure):
                 ("bh_dtheta", C.c_double), ("bh_kind", C.c_uint32), ("pad_", C.c_uint32), ("bh_spin", C.c_double),
                 ("bh_axis", C.c_double * 3), ("illum", C.c_uint32), ("adaptive", C.c_uint32),
                 ("thin_lens", C.c_uint32), ("env_hemi", C.c_uint32), ("microfacet_hemi", C.c_uint32),
-                ("pad2_", C.c_uint32)]
+                ("ext", C.c_uint32),  # RO_PARAMS_EXT: the record has the extension fields below
+                # the build's own features; all zero: the reference's frame
+                ("lensed_sky", C.c_uint32), ("disk_on", C.c_uint32), ("disk_flags", C.c_uint32),
+                ("pad3_", C.c_uint32), ("disk_r_in", C.c_double), ("disk_r_out", C.c_double),
+                ("disk_emission", C.c_float * 3), ("pad4_", C.c_float)]
+
+
+DISK_NO_REDSHIFT, DISK_LIGHT = 1, 16  # rrt_oracle.h RO_DISK_*
+N_EVENTS = 8                          # rrt_oracle.h RO_EV_N
+# ro_ray_query's record: status and out[15] unpacked
+RAY_DTYPE = np.dtype([("status", np.int32), ("steps", np.int32), ("bsdf", np.int32), ("t", np.float64),
+                      ("hit_p", np.float64, 3), ("n", np.float64, 3), ("rgb", np.float32, 3), ("e", np.float64, 3)])
 
 
 _lib = None
@@ -53,8 +64,12 @@ def lib():
         L.ro_scene_bvh.argtypes = [C.c_void_p, _f64p, _i32p, _u32p]
         L.ro_camera_load.argtypes = [C.c_char_p, C.POINTER(Camera), C.c_char_p, C.c_int]
         L.ro_params_default.argtypes = [C.POINTER(Params)]
+        L.ro_params_default_ext.argtypes = [C.POINTER(Params)]
         L.ro_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_uint32, C.c_uint32,
                                 C.c_uint32, C.c_uint32, _f32p, _i32p, C.c_void_p, C.c_void_p, C.c_int]
+        L.ro_render_events.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_uint32, C.c_uint32,
+                                       C.c_uint32, C.c_uint32, _f32p, _i32p, C.c_void_p, C.c_void_p, C.c_int]
+        L.ro_ray_query.argtypes = [C.c_void_p, C.POINTER(Params), _f64p, _f64p, C.c_int, _f64p]
         L.ro_pixel_key.restype = C.c_uint64
         L.ro_pixel_key.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
         L.ro_keyed_rand.argtypes = [C.c_uint64, C.c_uint32]
@@ -124,13 +139,17 @@ def load_camera(path):
 
 def make_params(frame_w, frame_h, ns_aa=1, max_ray_depth=1, ns_area_light=1, samples_per_batch=32,
                 max_tolerance=0.05, direct_hemisphere=False, seed=0, bh=(0.0, 1.0, 0.0, 0.1, 0.1), kerr=None,
-                illum=2, adaptive=True, thin_lens=False, env_hemi=False, microfacet_hemi=False):
+                illum=2, adaptive=True, thin_lens=False, env_hemi=False, microfacet_hemi=False, lensed_sky=False,
+                disk=None):
     """kerr: None (Schwarzschild) or (spin a/M, (ax, ay, az)) for the build-defined Kerr integrator.
     illum / adaptive / thin_lens / env_hemi / microfacet_hemi: the reference's compile-time switches
     (ILLUM, ADAPTIVE, THIN_LENS pathtracer.h:4-6, ENV_HEMI environment_light.h:4, MICROFACET_HEMI
-    bsdf.h:4), defaults as the reference build."""
+    bsdf.h:4), defaults as the reference build.
+    lensed_sky: RRT_SPACETIME_LENSED_SKY.  disk: None or a dict r_in, r_out (in M; r_in
+    resolved -- the restatement holds no ISCO formula), emission (3), redshift (True), light (False): the
+    plain accretion disk of rrt_set_disk."""
     p = Params()
-    lib().ro_params_default(C.byref(p))
+    lib().ro_params_default_ext(C.byref(p))
     p.ns_aa, p.max_ray_depth, p.ns_area_light = ns_aa, max_ray_depth, ns_area_light
     p.samples_per_batch, p.max_tolerance = samples_per_batch, max_tolerance
     p.direct_hemisphere, p.seed, p.frame_w, p.frame_h = int(direct_hemisphere), seed, frame_w, frame_h
@@ -141,6 +160,11 @@ def make_params(frame_w, frame_h, ns_aa=1, max_ray_depth=1, ns_area_light=1, sam
         p.bh_axis[0], p.bh_axis[1], p.bh_axis[2] = kerr[1]
     p.illum, p.adaptive, p.thin_lens = illum, int(adaptive), int(thin_lens)
     p.env_hemi, p.microfacet_hemi = int(env_hemi), int(microfacet_hemi)
+    p.lensed_sky = int(lensed_sky)
+    if disk is not None:
+        p.disk_on, p.disk_r_in, p.disk_r_out = 1, disk["r_in"], disk["r_out"]
+        p.disk_flags = (0 if disk.get("redshift", True) else DISK_NO_REDSHIFT) | (DISK_LIGHT if disk.get("light", False) else 0)
+        p.disk_emission[0], p.disk_emission[1], p.disk_emission[2] = disk.get("emission", (1.0, 1.0, 1.0))
     return p
 
 
@@ -189,6 +213,37 @@ def render(scene, cam, params, x0, y0, w, h, threads=None, counters=False):
     if rc != 0:
         raise RuntimeError("ro_render failed")
     return rgb, cnt, draws, ctr
+
+
+def render_events(scene, cam, params, x0, y0, w, h, threads=None):
+    """render that also returns the per-pixel event counts [h][w][N_EVENTS] (rrt_oracle.h
+    ro_render_events): (rgb, count, draws, events)."""
+    threads = threads or os.cpu_count() or 1
+    rgb = np.zeros((h, w, 3), np.float32)
+    cnt = np.zeros((h, w), np.int32)
+    draws = np.zeros((h, w), np.uint32)
+    ev = np.zeros((h, w, N_EVENTS), np.uint32)
+    rc = lib().ro_render_events(scene.h, C.byref(cam), C.byref(params), x0, y0, w, h, rgb, cnt, draws.ctypes.data,
+                                ev.ctypes.data, threads)
+    if rc != 0:
+        raise RuntimeError("ro_render_events failed (%d)" % rc)
+    return rgb, cnt, draws, ev
+
+
+def ray_query(scene, params, o, d, any_hit=False):
+    """ro_ray_query on rays (o [n, 3], d [n, 3]) under the params in force: RAY_DTYPE [n]."""
+    o = np.ascontiguousarray(o, np.float64).reshape(-1, 3)
+    d = np.ascontiguousarray(d, np.float64).reshape(-1, 3)
+    rec = np.zeros(len(o), RAY_DTYPE)
+    out = np.zeros(15)
+    for i in range(len(o)):
+        st = lib().ro_ray_query(scene.h, C.byref(params), o[i], d[i], int(any_hit), out)
+        if st < 0:
+            raise RuntimeError("ro_ray_query failed (%d)" % st)
+        r = rec[i]
+        r["status"], r["steps"], r["bsdf"], r["t"] = st, int(out[0]), int(out[14]), out[1]
+        r["hit_p"], r["n"], r["rgb"], r["e"] = out[2:5], out[5:8], out[8:11], out[11:14]
+    return rec
 
 
 LIBM_FN = {"sin": 0, "cos": 1, "acos": 2, "atan2": 3, "sinf": 4, "cosf": 5, "exp": 6, "log": 7, "erf": 8, "atan": 9,

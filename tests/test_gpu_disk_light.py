@@ -304,8 +304,16 @@ def test_every_entry_point_gives_the_same_frame(gpu, mode):
     crop, ccnt, _, _ = gpu.render(p, 37, 5, 8, 5)
     assert np.array_equal(u32(crop), u32(rgb[5:10, 37:45])) and (ccnt == 1).all()
     deep = rrt.render_params(W, H, ns_aa=1, max_ray_depth=3, ns_area_light=2)
-    a, _, _, name = render(gpu, deep)  # depth >= 2 takes the term at every level through one_bounce
+    a, acnt, adraws, name = render(gpu, deep)  # depth >= 2 takes the term at every level through one_bounce
     assert ("<true, false, 10," if mode == "blackbody" else "<true, false, 9,") in name and np.isfinite(a).all()
+    if mode == "plain":
+        # the restatement's frame bit for bit (tests/test_gpu_deep_builds.py case 8 has the mirror and the
+        # glass sphere, jitter and the adaptive loop; the blackbody colour differs in the disk's rgb alone)
+        ol = lc.ol
+        pr = ol.make_params(W, H, ns_aa=1, max_ray_depth=3, ns_area_light=2, bh=BH, kerr=dc.KERRS["a0.9"],
+                            disk=dict(r_in=gpu.get_disk()["r_in"], r_out=dc.R_OUT, emission=EM, light=True))
+        ref = ol.render(ol.Scene(SPHERES), ol.load_camera(Case(lc.WIDE_CASE).camera_path), pr, 0, 0, W, H, threads=16)
+        assert np.array_equal(u32(a), u32(ref[0])) and np.array_equal(acnt, ref[1]) and np.array_equal(adraws, ref[2])
 
 
 @pytest.mark.parametrize("name,depth,flags", [("wavefront", 3, rrt.RRT_RENDER_WAVEFRONT), ("deep_sample", 3, rrt.RRT_RENDER_DEEP_SAMPLE),
