@@ -13,6 +13,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#define RRT_DEVICE_ADDRESS_SPACES 1  // KParams' pointers carry their address spaces in device code
 #include "rrt_internal.h"
 #include "../../include/rrt.h"  // RRT_AUDIT_* proof kinds
 #include "rrt_rng.h"
@@ -24,6 +25,29 @@
 #define EPS_D 0.00000000001
 
 namespace rrt {
+
+// ------------------------------------------------------------------ LDS-qualified access
+// A volatile access through a generic pointer stays a flat instruction (a 64-bit VGPR address, both
+// wait counters): the compiler's address-space inference does not rewrite volatile accesses.  The
+// kernels therefore name their __shared__ objects through an LDS-qualified reference (lds_of, at
+// the object's declaration) and the volatile accessors take LDS-qualified pointers only, so every
+// access is a ds_read / ds_write and a pointer that is not LDS does not compile.
+#define RRT_LDS __attribute__((address_space(3)))
+// x must be a __shared__ object (or a generic reference to one: heavy_pixel_block's arguments)
+template <class T>
+__device__ __forceinline__ RRT_LDS T& lds_of(T& x) { return *(RRT_LDS T*)&x; }
+template <class T>
+__device__ __forceinline__ void lput(RRT_LDS T* a, uint32_t i, T v) { ((volatile RRT_LDS T*)a)[i] = v; }
+template <class T>
+__device__ __forceinline__ T lget(const RRT_LDS T* a, uint32_t i) { return ((const volatile RRT_LDS T*)a)[i]; }
+// A wave-uniform constant-space pointer that arrived in VGPRs (an out-of-line callee's argument), in
+// SGPRs: reads through it take the scalar path
+template <class T>
+__device__ __forceinline__ const RRT_CONST_AS T* uniform_ptr(const RRT_CONST_AS T* p) {
+  const uint64_t a = (uint64_t)p;
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
+  return (const RRT_CONST_AS T*)(((uint64_t)hi << 32) | lo);
+}
 
 // ------------------------------------------------------------------ Vector3D (double)
 struct v3 { double x, y, z; };
@@ -239,8 +263,12 @@ __device__ __forceinline__ bool segment_clear(const DGrid& g, v3 o, double max_t
 // tmax < 0.  Nothing else of the walk runs, so skipping it (and the reciprocals it needs) is
 // result-identical.
 __device__ __forceinline__ bool segment_outside_root(const KParams& kp, v3 o, v3 e) {
-  return fmax(o.x, e.x) < kp.root_lo[0] || fmin(o.x, e.x) > kp.root_hi[0] || fmax(o.y, e.y) < kp.root_lo[1] ||
-         fmin(o.y, e.y) > kp.root_hi[1] || fmax(o.z, e.z) < kp.root_lo[2] || fmin(o.z, e.z) > kp.root_hi[2];
+  // the six bounds read together (one scalar load each way), then compared without branches: behind
+  // short-circuit branches each bound was its own load, wait and branch
+  const double l0 = kp.root_lo[0], l1 = kp.root_lo[1], l2 = kp.root_lo[2];
+  const double h0 = kp.root_hi[0], h1 = kp.root_hi[1], h2 = kp.root_hi[2];
+  return ((int)(fmax(o.x, e.x) < l0) | (int)(fmin(o.x, e.x) > h0) | (int)(fmax(o.y, e.y) < l1) |
+          (int)(fmin(o.y, e.y) > h1) | (int)(fmax(o.z, e.z) < l2) | (int)(fmin(o.z, e.z) > h2)) != 0;
 }
 // Sphere::test + the range checks of Sphere::intersect (sphere.cpp:10-53), min_t = 0
 __device__ __forceinline__ bool sphere_t(v3 c, double r2, v3 o, v3 d, double max_t, double& t) {
@@ -445,9 +473,9 @@ __device__ __forceinline__ bool traverse_free(const KParams& kp, v3 o, v3 d, v3 
     for (;;) {
       const bool big = bi < nb;
       if (!big && node < 0) break;
-      const DNode* n = big ? nullptr : &kp.free_nodes[node];
-      const double* mn = big ? kp.big[bi].mn : n->mn;
-      const double* mx = big ? kp.big[bi].mx : n->mx;
+      const RRT_CONST_AS DNode* n = big ? nullptr : &kp.free_nodes[node];
+      const RRT_CONST_AS double* mn = big ? kp.big[bi].mn : n->mn;
+      const RRT_CONST_AS double* mx = big ? kp.big[bi].mx : n->mx;
       const int first = big ? kp.big[bi].first : n->first;
       const int count = big ? kp.big[bi].count : n->count;
       bool pass = !big || leaf_may_hit<COUNT>(kp, first, count, o, e, cn);
@@ -1322,8 +1350,14 @@ __device__ __forceinline__ int occ_exit(const KParams& kp, v3 a, v3 b, double m)
 }
 // occ_exit out of line, one copy per kernel build W (inline or the whole proof out of
 // line measured slower)
+// (an out-of-line callee sees a `const KParams&` as a generic pointer and would read it through
+// flat loads: it takes the launch block by its address space and names it generic again inside,
+// where the compiler follows the cast; arguments arrive in VGPRs, so the wave-uniform address goes
+// to SGPRs first and the reads take the scalar path)
 template <int W>
-__device__ __noinline__ int occ_exit_call(const KParams& kp, v3 a, v3 b, double m) { return occ_exit(kp, a, b, m); }
+__device__ __noinline__ int occ_exit_call(const RRT_CONST_AS KParams* kpq, v3 a, v3 b, double m) {
+  return occ_exit(*(const KParams*)uniform_ptr(kpq), a, b, m);
+}
 __device__ __forceinline__ bool occ_inside(const DShadowProof& sp, v3 b) {
   return b.x >= sp.in_lo[0] && b.x <= sp.in_hi[0] && b.y >= sp.in_lo[1] && b.y <= sp.in_hi[1] && b.z >= sp.in_lo[2] &&
          b.z <= sp.in_hi[2];
@@ -1483,7 +1517,7 @@ __device__ __forceinline__ bool shadow_occluded_proof(const KParams& kp, v3 o, v
       const double ia = mp.rho / vprev;
       const v3 pa = V(c.x + (ea * ia) * X.x + (eb * ia) * Y.x, c.y + (ea * ia) * X.y + (eb * ia) * Y.y,
                       c.z + (ea * ia) * X.z + (eb * ia) * Y.z);
-      const int res = occ_exit_call<W>(kp, pa, pb, m);
+      const int res = occ_exit_call<W>((const RRT_CONST_AS KParams*)&kp, pa, pb, m);
       if (res) return res > 0;
     }
     a_in = b_in;
@@ -1654,15 +1688,16 @@ __device__ __forceinline__ bool camera_miss_proof(const KParams& kp, v3 o, v3 d,
 // W: the calling kernel build's tag -- one copy per build, since a callee shared by builds of
 // different waves-per-SIMD budgets takes the smallest budget's registers for all of them
 template <bool COUNT, int W>
-__device__ __noinline__ bool camera_miss_proof_call(const KParams& kp, v3 o, v3 d, Counters& cn) {
-  return camera_miss_proof<COUNT>(kp, o, d, cn);
+__device__ __noinline__ bool camera_miss_proof_call(const RRT_CONST_AS KParams* kpq, v3 o, v3 d, Counters& cn) {
+  return camera_miss_proof<COUNT>(*(const KParams*)uniform_ptr(kpq), o, d, cn);
 }
 // NI: out of line (the register-heavy per-pixel-loop builds keep their occupancy), W its build tag
 template <bool COUNT, bool KERR, bool NI = false, int W = 0>
 __device__ __forceinline__ bool camera_proven_miss(const KParams& kp, v3 o, v3 d, Counters& cn) {
   if (KERR || !kp.miss.on || (COUNT && !kp.count_exec)) return false;
   RRT_T0(tp0);
-  const bool r = NI ? camera_miss_proof_call<COUNT, W>(kp, o, d, cn) : camera_miss_proof<COUNT>(kp, o, d, cn);
+  const bool r = NI ? camera_miss_proof_call<COUNT, W>((const RRT_CONST_AS KParams*)&kp, o, d, cn)
+                    : camera_miss_proof<COUNT>(kp, o, d, cn);
   RRT_ACC(t_proof, tp0);
   if (COUNT && r && kp.audit && audit_pick(kp, o, d)) {
     Counters c2 = {};

@@ -5,6 +5,26 @@
 
 #include "rrt_blackbody.h"
 
+// Address spaces of the device pointers below, stated in the device code's view of
+// these structs (rrt_device.h sets RRT_DEVICE_ADDRESS_SPACES; the host side sees plain pointers of
+// the same size).  A load through a generic pointer is a flat instruction: a 64-bit VGPR address,
+// both wait counters, no scalar path.
+//   RRT_CONST_AS:  nothing writes the array between a launch's start and its end (the scene tables
+//                  rrt_set_scene builds, the environment map's tables, the launch's tile lists):
+//                  constant address space -- global_load with an SGPR base, s_load where the
+//                  address is wave-uniform.
+//   RRT_GLOBAL_AS: written during the launch by this kernel or one running beside it (claim
+//                  counters and lists, continuation records, sample 0, outputs, counters): plain
+//                  global, with the atomics and ordering each use states -- the scalar cache is not
+//                  coherent with those stores.
+#if defined(__HIP_DEVICE_COMPILE__) && defined(RRT_DEVICE_ADDRESS_SPACES)
+#define RRT_CONST_AS __attribute__((address_space(4)))
+#define RRT_GLOBAL_AS __attribute__((address_space(1)))
+#else
+#define RRT_CONST_AS
+#define RRT_GLOBAL_AS
+#endif
+
 #define RRT_MAX_LIGHTS 16
 #define RRT_MAX_BSDFS 64
 #define RRT_MAX_DEPTH 16
@@ -73,10 +93,10 @@ struct DLight {
 // tables the reference builds in init() (pdf, per-row conditional CDFs, marginal CDF), all on
 // the host with the reference's arithmetic.  w == 0: no environment map.
 struct DEnv {
-  const float* tex;      // [h][w][3] Spectrum
-  const double* pdf;     // [h][w] normalised pdf_envmap
-  const double* conds;   // [h][w] conds_y
-  const double* marg;    // [h]    marginal_y
+  const RRT_CONST_AS float* tex;      // [h][w][3] Spectrum
+  const RRT_CONST_AS double* pdf;     // [h][w] normalised pdf_envmap
+  const RRT_CONST_AS double* conds;   // [h][w] conds_y
+  const RRT_CONST_AS double* marg;    // [h]    marginal_y
   uint32_t w, h;
 };
 
@@ -105,7 +125,7 @@ struct DHole {
 // every leaf slab test fails, no primitive is tested, and the reference's traversal returns
 // "no hit" -- the traversal can be skipped without changing any result.
 struct DGrid {
-  const uint8_t* k;   // [n[2]][n[1]][n[0]]; null = no grid
+  const RRT_CONST_AS uint8_t* k;   // [n[2]][n[1]][n[0]]; null = no grid
   double g0[3];       // root box minimum
   double inv_h;       // 1 / cell size
   double h_free;      // cell size * (1 - 2^-20): the free radius of value k is (k - 2) * h_free
@@ -228,26 +248,26 @@ enum { RRT_HEAVY_LIST = 0, RRT_HEAVY_DRAIN = 1 };
 
 struct KParams {
   // scene
-  const DNode* nodes;
-  const DPrimGeo* geo;
-  const DPrimNrm* nrm;
-  const DPrimMeta* meta;
-  const DBsdf* bsdfs;
-  const DLight* lights;
+  const RRT_CONST_AS DNode* nodes;
+  const RRT_CONST_AS DPrimGeo* geo;
+  const RRT_CONST_AS DPrimNrm* nrm;
+  const RRT_CONST_AS DPrimMeta* meta;
+  const RRT_CONST_AS DBsdf* bsdfs;
+  const RRT_CONST_AS DLight* lights;
   uint32_t n_lights;
   uint32_t fast_div;  // scene bounds allow the Markstein-corrected slab quotients
   DGrid grid;
-  const DNode* clean_nodes;   // clean tree (pad = first leaf ordinal); null: reference walk only
-  const DPlane* planes;       // per leaf slot; null: no plane cull
+  const RRT_CONST_AS DNode* clean_nodes;   // clean tree (pad = first leaf ordinal); null: reference walk only
+  const RRT_CONST_AS DPlane* planes;       // per leaf slot; null: no plane cull
   double root_lo[3], root_hi[3];  // root box widened by plane_eps (segment_outside_root)
   double plane_eps;           // plane-cull margin (scene-scaled, ~1e6 x rounding error)
-  const DBig* big;            // oversized leaves by left-first ordinal
-  const uint32_t* big_mask;   // per grid cell: oversized leaves with a primitive in reach, or null
+  const RRT_CONST_AS DBig* big;            // oversized leaves by left-first ordinal
+  const RRT_CONST_AS uint32_t* big_mask;   // per grid cell: oversized leaves with a primitive in reach, or null
   double big_reach;           // segments shorter than this may use big_mask ((RRT_BIG_REACH - 1) h_free)
   int32_t clean_root;         // 0, or -1 if every leaf is oversized
   uint32_t n_big;
-  const DNode* free_nodes;    // search tree over the clean tree's leaves (traverse_free), or null
-  const DNode4* free4;        // the same tree 4 wide (traverse_free4), or null (binary walk)
+  const RRT_CONST_AS DNode* free_nodes;    // search tree over the clean tree's leaves (traverse_free), or null
+  const RRT_CONST_AS DNode4* free4;        // the same tree 4 wide (traverse_free4), or null (binary walk)
   double free4_omax;          // segments starting farther out (max |coordinate|) take the binary walk
   DCamera cam;
   DHole hole;
@@ -263,13 +283,13 @@ struct KParams {
   double frame_w, frame_h;
   uint32_t frame_wi, frame_hi;
   // work: list of tiles (x, y), each split into 8x8 pixel blocks pulled by waves
-  const uint32_t* tiles;
+  const RRT_CONST_AS uint32_t* tiles;
   uint32_t n_tiles, tile_size;
   uint32_t blocks_per_tile_side, n_blocks;
-  uint32_t* block_counter;
+  RRT_GLOBAL_AS uint32_t* block_counter;
   // sample-parallel kernel (rrt_sample.hip rrt_batch_kernel)
   uint32_t n_pixels;     // n_tiles * tile_size^2 (pixel work items)
-  const uint32_t* tile_order;  // claim order over the caller's tile list
+  const RRT_CONST_AS uint32_t* tile_order;  // claim order over the caller's tile list
   // claim queues (one per XCD): queue q holds claim indices [q_end[q-1], q_end[q]) of tile_order,
   // its counter is block_counter[RRT_QUEUE_STRIDE * q]; a block starts on queue blockIdx % n_queues
   uint32_t n_queues;
@@ -277,24 +297,24 @@ struct KParams {
   uint32_t q_stripe;     // 1: queue q holds claims q, q + n_queues, ... of the whole order (q_end unused)
   // pixel miss proof (rrt_pixel_proof_kernel): the claim indices whose pixels were not proven
   // all-miss, in claim order per wave, and their count; null: every pixel is claimed
-  uint32_t* claim_list;
-  uint32_t* claim_count;
+  RRT_GLOBAL_AS uint32_t* claim_list;
+  RRT_GLOBAL_AS uint32_t* claim_count;
   struct FirstSample { float r, g, b; uint32_t hit; };
-  FirstSample* first;          // sample 0 of every pixel slot (rrt_first_kernel), or null
+  RRT_GLOBAL_AS FirstSample* first;          // sample 0 of every pixel slot (rrt_first_kernel), or null
   uint32_t group;        // lanes per pixel (power of two, 2..32)
   uint32_t draws_miss;   // RNG draws of a camera sample whose query misses (jitter: 2)
   uint32_t draws_hit;    // ... and of one that hits (jitter + the direct-lighting sampler draws)
   uint32_t clip_x0, clip_y0, clip_x1, clip_y1;  // region actually requested (exclusive end)
   // outputs, packed per tile: pixel (i, j) of tile t at t*tile_size^2 + j*tile_size + i
-  float* rgb;
-  int32_t* count;
-  uint32_t* draws;      // optional
-  uint32_t* counters;   // optional [4] per pixel
+  RRT_GLOBAL_AS float* rgb;
+  RRT_GLOBAL_AS int32_t* count;
+  RRT_GLOBAL_AS uint32_t* draws;      // optional
+  RRT_GLOBAL_AS uint32_t* counters;   // optional [4] per pixel
   DShadowProof occ;     // the hot fields above keep their offsets
   // heavy pixels (rrt_pixel_proof_kernel pixel_heavy -> rrt_heavy_kernel): listed pixels rendered
   // slot-parallel, one wave per pixel and a step's 64 draw-offset slots per round
-  uint32_t* heavy_list;   // claim indices (null: no heavy path)
-  uint32_t* heavy_count;  // [0]: entries appended by the pass (capped at heavy_cap); [1]: entries taken
+  RRT_GLOBAL_AS uint32_t* heavy_list;   // claim indices (null: no heavy path)
+  RRT_GLOBAL_AS uint32_t* heavy_count;  // [0]: entries appended by the pass (capped at heavy_cap); [1]: entries taken
   uint32_t heavy_cap;     // list capacity
   uint32_t claim_back;    // batch kernel: hinted list entries at the front (claim_count[0] of them),
                           // the others from the list's end backwards (claim_count[1])
@@ -311,7 +331,7 @@ struct KParams {
   uint32_t sw_pad;
   // the path pool kernel (rrt_path.hip, depth >= 2): each path's per-level terms of
   // at_least_one_bounce_radiance, [level][field][path] (RRT_PATH_FIELDS floats a level)
-  float* path_stack;
+  RRT_GLOBAL_AS float* path_stack;
   // batch kernel: a wave whose oldest pixel has run this long (wall-clock ticks, 100 MHz) takes
   // issue priority 2, four times as long priority 3 (rrt_sample.hip tail_prio)
   uint32_t prio_ticks;
@@ -319,18 +339,18 @@ struct KParams {
   DKerrProof kproof;      // Kerr builds: the shadow rays' occlusion proof (kp.occ's face triangles)
   // the pixel pass's first level (rrt_strip_proof_kernel): strips of 64 consecutive claim indices
   // proven as wholes -- flag 1 per strip -- before the per-pixel level (null: per-pixel pass only)
-  uint32_t* strip_list;
+  RRT_GLOBAL_AS uint32_t* strip_list;
   // run-time proof audit (rrt_device.h audit_pick): counting launches re-check every
   // 2^audit_shift-th proven ray (and pixel) against the exact march; tallies [2 k] checked,
   // [2 k + 1] violations per proof k (RRT_AUDIT_*); null: no audit
-  unsigned long long* audit;  // 64-bit: a 1080p frame audited at every_log2 = 0 exceeds 2^32 checks
+  RRT_GLOBAL_AS unsigned long long* audit;  // 64-bit: a 1080p frame audited at every_log2 = 0 exceeds 2^32 checks
   uint32_t audit_shift, audit_pad;
   // continuations: a batch-kernel group whose pixel still has >= cont_min_left
   // samples to go after an adaptive check hands it to a heavy block that is waiting for work
   // (cont_ctl[RRT_CONT_IDLE] > 0), which renders the remaining steps' draw-offset slots in parallel.
   // cont null: off.  Waiting blocks stop once all batch_waves batch waves are past their last pixel.
-  ContRec* cont;
-  uint32_t* cont_ctl;
+  RRT_GLOBAL_AS ContRec* cont;
+  RRT_GLOBAL_AS uint32_t* cont_ctl;
   uint32_t cont_cap, cont_min_left;
   uint32_t cont_seq, batch_waves;
   uint32_t cont_room;     // batch blocks that leave at once, room for the waiting heavy blocks
@@ -342,7 +362,7 @@ struct KParams {
   // diagnostic build: per-wave progress records in host-coherent memory (RRT_WATCHDOG_MS), read by
   // the host while the kernels run: [wave][4] = {iteration, state, pixel, marker}; batch waves
   // first, the heavy kernel's blocks from RRT_WD_HEAVY on
-  uint32_t* wd;
+  RRT_GLOBAL_AS uint32_t* wd;
 #endif
 };
 // One launch of the ray-query kernels (rrt_query.hip), passed by value beside the KParams (which

@@ -48,10 +48,11 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
+// volatile LDS-qualified accesses (ds_read / ds_write; a pointer that is not LDS does not compile)
 template <class T>
-__device__ __forceinline__ void pput(T* a, uint32_t i, T v) { ((volatile T*)a)[i] = v; }
+__device__ __forceinline__ void pput(RRT_LDS T* a, uint32_t i, T v) { lput(a, i, v); }
 template <class T>
-__device__ __forceinline__ T pget(const T* a, uint32_t i) { return ((const volatile T*)a)[i]; }
+__device__ __forceinline__ T pget(const RRT_LDS T* a, uint32_t i) { return lget(a, i); }
 
 // the n-th (from 0) set bit of m; n < popcount(m)
 __device__ __forceinline__ uint32_t nth_bit(uint64_t m, uint32_t n) {
@@ -87,8 +88,12 @@ struct OwnLds {
 namespace rrt {
 
 // the block's ray slots and owned-path state (one kernel in this unit uses them)
-__shared__ PathLds pl;
-__shared__ OwnLds ol;
+// (each function below names them through LDS-qualified references `pl` and `ol`)
+__shared__ PathLds pl_mem;
+__shared__ OwnLds ol_mem;
+#define RRT_PATH_LDS_REFS                    \
+  RRT_LDS PathLds& pl = lds_of(rrt::pl_mem); \
+  RRT_LDS OwnLds& ol = lds_of(rrt::ol_mem)
 
 // per-path global slots: level `lv` of the recursion's terms, and the pixel record (level
 // max_ray_depth: pixel, output slot, samples, sums, the sample's emission)
@@ -100,6 +105,7 @@ __device__ __forceinline__ uint32_t* rec(const KParams& kp, uint32_t field) {
 }
 // Camera::generate_ray at the sample's jitter (part1_code.cpp:132-141, 182-187) into R1
 __device__ __forceinline__ void start_sample(const KParams& kp, Rng& g, uint32_t t) {
+  RRT_LDS PathLds& pl = lds_of(rrt::pl_mem);
   const DCamera& cam = kp.cam;
   const uint32_t pxy = *rec(kp, 0);
   double sx = (double)(pxy & 0xffffu), sy = (double)(pxy >> 16);
@@ -118,6 +124,7 @@ __device__ __forceinline__ void start_sample(const KParams& kp, Rng& g, uint32_t
 // pending << 5; the rest of the path's state goes back to LDS and its global slots.
 template <int W>
 __device__ __forceinline__ uint32_t path_phase(const KParams& kp, uint32_t st) {
+  RRT_PATH_LDS_REFS;
   const uint32_t t = threadIdx.x;
   const bool deep = kp.max_ray_depth >= 2;
   const bool hemi = kp.direct_hemisphere != 0;
@@ -320,7 +327,10 @@ extern "C" int rrt_prof_read_path(unsigned long long* out) {  // out: 8; resets
 template <int WAVES>
 __global__ __launch_bounds__(256, WAVES) void rrt_path_kernel(const KParams* __restrict__ kpp0) {
   using namespace rrt;
-  const KParams* kpp = kpp0;
+  RRT_PATH_LDS_REFS;
+  // (by its address space: behind the asm below the pointer is no longer known to be the kernel
+  // argument, and a generic one would make every re-read a flat load)
+  const RRT_CONST_AS KParams* kpp = (const RRT_CONST_AS KParams*)kpp0;
   const uint32_t t = threadIdx.x, lane = t & 63u, wb = t - lane;
   const uint64_t lt = (1ull << lane) - 1ull;
   const uint32_t n_claims = kpp0->claim_list ? *kpp0->claim_count : kpp0->n_pixels;
@@ -339,7 +349,7 @@ __global__ __launch_bounds__(256, WAVES) void rrt_path_kernel(const KParams* __r
     // The launch constants are re-read from the constant cache each round: hoisted out of the loop
     // they would all stay live (in VGPRs, once the SGPRs run out) across the query
     asm volatile("" : "+s"(kpp));
-    const KParams& kp = *kpp;
+    const KParams& kp = *(const KParams*)kpp;
     const uint32_t ts = kp.tile_size, tpix = ts * ts;
     const bool hemi = kp.direct_hemisphere != 0;
     const DCamera& cam = kp.cam;

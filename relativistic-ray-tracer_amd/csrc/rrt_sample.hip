@@ -30,14 +30,12 @@ struct ColdLds : ShadeLds {  // + the per-pixel sums of the lane-per-pixel kerne
   float rr[256], rg[256], rb[256];
 };
 
-template <class T>
-__device__ __forceinline__ void lput(T* a, uint32_t i, T v) { ((volatile T*)a)[i] = v; }
-template <class T>
-__device__ __forceinline__ T lget(const T* a, uint32_t i) { return ((const volatile T*)a)[i]; }
+// (lput / lget, rrt_device.h: volatile LDS-qualified accesses; every `cl`, `sh`, `gs` below is an
+// LDS-qualified reference to one of this unit's __shared__ objects)
 
 // park a camera-hit record in the lane's LDS slots
 template <class SL>
-__device__ __forceinline__ void park_hit(SL& cl, uint32_t t, const Isect& is0) {
+__device__ __forceinline__ void park_hit(RRT_LDS SL& cl, uint32_t t, const Isect& is0) {
   for (int k = 0; k < 3; ++k) {
     lput(cl.hp[k], t, (&is0.hit_p.x)[k]);
     lput(cl.nn[k], t, (&is0.n.x)[k]);
@@ -50,7 +48,7 @@ __device__ __forceinline__ void park_hit(SL& cl, uint32_t t, const Isect& is0) {
 // (park_hit), re-read per light sample so no hit state stays live across the shadow queries.
 // W: the calling kernel build's tag for the out-of-line occlusion proof (rrt_device.h query_nx)
 template <bool COUNT, int LEAN, int W = 0, class SL = ShadeLds>
-__device__ __forceinline__ spec direct_importance_parked(const KParams& kp, Rng& g, SL& cl, uint32_t t, Counters& cn) {
+__device__ __forceinline__ spec direct_importance_parked(const KParams& kp, Rng& g, RRT_LDS SL& cl, uint32_t t, Counters& cn) {
   const uint32_t bsdf = lget(cl.bsdf, t);
   spec L = S(0, 0, 0);
   int total = 0;
@@ -77,7 +75,7 @@ __device__ __forceinline__ spec direct_importance_parked(const KParams& kp, Rng&
   return L / (float)total;
 }
 template <bool COUNT, int LEAN, int W = 0>
-__device__ __forceinline__ spec direct_importance_lds(const KParams& kp, Rng& g, const Isect& is0, ColdLds& cl, uint32_t t,
+__device__ __forceinline__ spec direct_importance_lds(const KParams& kp, Rng& g, const Isect& is0, RRT_LDS ColdLds& cl, uint32_t t,
                                       Counters& cn) {
   park_hit(cl, t, is0);
   return direct_importance_parked<COUNT, LEAN, W>(kp, g, cl, t, cn);
@@ -85,7 +83,7 @@ __device__ __forceinline__ spec direct_importance_lds(const KParams& kp, Rng& g,
 
 // estimate_direct_lighting_hemisphere (part1_code.cpp:15-31) for the parked hit
 template <bool COUNT, int LEAN>
-__device__ __forceinline__ spec direct_hemisphere_parked(const KParams& kp, Rng& g, ShadeLds& cl, uint32_t t, Counters& cn) {
+__device__ __forceinline__ spec direct_hemisphere_parked(const KParams& kp, Rng& g, RRT_LDS ShadeLds& cl, uint32_t t, Counters& cn) {
   const uint32_t bsdf = lget(cl.bsdf, t);
   const int num = (int)(kp.n_lights * kp.ns_area_light);
   spec L = S(0, 0, 0);
@@ -104,7 +102,7 @@ __device__ __forceinline__ spec direct_hemisphere_parked(const KParams& kp, Rng&
   return ((L * 2.0f) * (float)PI_D) / (float)num;
 }
 template <bool COUNT, int LEAN>
-__device__ __forceinline__ spec direct_hemisphere_lds(const KParams& kp, Rng& g, const Isect& is0, ColdLds& cl, uint32_t t,
+__device__ __forceinline__ spec direct_hemisphere_lds(const KParams& kp, Rng& g, const Isect& is0, RRT_LDS ColdLds& cl, uint32_t t,
                                       Counters& cn) {
   park_hit(cl, t, is0);
   return direct_hemisphere_parked<COUNT, LEAN>(kp, g, cl, t, cn);
@@ -171,7 +169,8 @@ template <bool COUNT, int LEAN, int WAVES, bool DEEP = false>
 __global__ __launch_bounds__(256, WAVES) void rrt_sample_kernel(const KParams* __restrict__ kpp) {
   const KParams& kp = *kpp;
   using namespace rrt;
-  __shared__ ColdLds cl;
+  __shared__ ColdLds cl_mem;
+  RRT_LDS ColdLds& cl = lds_of(cl_mem);
   const uint32_t t = threadIdx.x;
   const uint32_t lane = t & 63u;
   const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64u - lane));
@@ -484,9 +483,15 @@ __device__ bool cont_wait_take(const KParams& kp, HeavyState<NW>& hs) {
   return got;
 }
 template <int LEAN, int W, int NW>
-__device__ __noinline__ void heavy_pixel_block(const KParams& kp, rrt::ShadeLdsN<64 * NW>& sh, HeavyState<NW>& hs,
-                                               uint32_t t, rrt::Counters& cn) {
+__device__ __noinline__ void heavy_pixel_block(const RRT_CONST_AS KParams* kpq, rrt::ShadeLdsN<64 * NW>& sh_gen,
+                                               HeavyState<NW>& hs_gen, uint32_t t, rrt::Counters& cn) {
   using namespace rrt;
+  // the launch block, by its address space and in SGPRs (rrt_device.h occ_exit_call)
+  const KParams& kp = *(const KParams*)uniform_ptr(kpq);
+  // the callers' __shared__ HeavyLds members (rrt_heavy_kernel's `hl`), handed over as generic
+  // references: an out-of-line callee takes no LDS-qualified pointer
+  RRT_LDS ShadeLdsN<64 * NW>& sh = lds_of(sh_gen);
+  RRT_LDS HeavyState<NW>& hs = lds_of(hs_gen);
   constexpr uint32_t NS = 64u * NW;  // slots per round
   const uint32_t Dm = kp.draws_miss, Dh = kp.draws_hit, S1 = Dh / Dm;
   const DCamera& cam = kp.cam;
@@ -604,7 +609,7 @@ __global__ __launch_bounds__(64 * NW, HW) void rrt_heavy_kernel(const KParams* _
     const uint64_t w_h = wall_clock64();
     const uint32_t pslot = hs.slot;
 #endif
-    heavy_pixel_block<LEAN, RRT_OCC_TAG_SLOT(LEAN, HW) ? RRT_OCC_TAG_SLOT(LEAN, HW) + 32 * NW : 0, NW>(kp, hl.sh, hs, t, cn);
+    heavy_pixel_block<LEAN, RRT_OCC_TAG_SLOT(LEAN, HW) ? RRT_OCC_TAG_SLOT(LEAN, HW) + 32 * NW : 0, NW>((const RRT_CONST_AS KParams*)kpp, hl.sh, hs, t, cn);
 #if RRT_PROFILE
     if (wd && t == 0) wd[3] = 0x12u;  // pixel done
     if (t == 0 && pslot < (1u << 21)) {  // elapsed ticks; "rounds" 1
@@ -667,15 +672,17 @@ template <int LEAN, int WAVES>
 __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __restrict__ kpp) {
   const KParams& kp = *kpp;
   using namespace rrt;
-  __shared__ ShadeLds cl;
+  __shared__ ShadeLds cl_mem;
+  RRT_LDS ShadeLds& cl = lds_of(cl_mem);
   constexpr uint32_t RRT_SLOTS = SlotWindow<LEAN>::n;
   constexpr uint32_t STRIPE = RRT_STRIPE_OF(LEAN);
   // the claim space (a multiple of 64 pixels: tiles of 8k x 8k) must hold whole stripes
   static_assert(STRIPE > 0 && 64u % STRIPE == 0, "RRT_STRIPE must divide 64");
-  __shared__ GroupLds<RRT_SLOTS> gs;
-  float* const fr = cl.cr;  // per-lane sample radiance for the ordered fold (free after shading)
-  float* const fg = cl.cg;
-  float* const fb = cl.cb;
+  __shared__ GroupLds<RRT_SLOTS> gs_mem;
+  RRT_LDS GroupLds<RRT_SLOTS>& gs = lds_of(gs_mem);
+  RRT_LDS float* const fr = cl.cr;  // per-lane sample radiance for the ordered fold (free after shading)
+  RRT_LDS float* const fg = cl.cg;
+  RRT_LDS float* const fb = cl.cb;
   const uint32_t t = threadIdx.x;
   const uint32_t lane = t & 63u;
   const uint32_t G = kp.group;
@@ -1238,7 +1245,8 @@ template <int LEAN, int WAVES>
 __global__ __launch_bounds__(256, WAVES) void rrt_first_kernel(const KParams* __restrict__ kpp) {
   const KParams& kp = *kpp;
   using namespace rrt;
-  __shared__ ShadeLds cl;
+  __shared__ ShadeLds cl_mem;
+  RRT_LDS ShadeLds& cl = lds_of(cl_mem);
   const uint32_t t = threadIdx.x;
   const uint32_t ts = kp.tile_size, tpix = ts * ts;
   const DCamera& cam = kp.cam;
