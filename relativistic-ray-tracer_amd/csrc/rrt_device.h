@@ -860,50 +860,11 @@ __device__ __forceinline__ bool segment_query(const KParams& kp, v3 o, v3 d, dou
 }
 
 // ------------------------------------------------------------------ kernel variants
-// The integrator templates take an int variant V (named LEAN at the use sites):
-//   0 general, Schwarzschild;  1 LEAN: area lights only, no microfacet BSDF, importance-sampled
-//   direct light;  2 LEAN with point lights too;  V_KERR general with the Kerr march.
-// Each variant is its own kernel build, so no build carries code (and registers) it never runs.
-constexpr int V_KERR = 3;
-// V_SW: the general Schwarzschild build with the reference's compile-time switches as run-time
-// flags (KParams::sw; include/rrt.h RRT_RENDER_THIN_LENS .. RRT_RENDER_ILLUM_MASK)
-constexpr int V_SW = 4;
+// The integrator templates take an int variant V (named LEAN at the use sites): the builds V_* and
+// their is_* predicates of rrt_internal.h, which the host's choice (rrt_host.cpp choose_variant) shares.
+// V_SW's switches (KParams::sw):
 enum { SW_THIN_LENS = 1u, SW_NO_ADAPTIVE = 2u, SW_ENV_HEMI = 4u, SW_MF_HEMI = 8u };
 __device__ __forceinline__ uint32_t sw_illum(const KParams& kp) { return ((kp.sw >> 4) & 3u) ^ 2u; }  // ILLUM
-// V_SKY / V_KERR_SKY: the general builds with the lensed sky (RRT_SPACETIME_LENSED_SKY):
-// every query runs the exit-mode march and an escaping ray looks the environment map up along its
-// exit direction.  Per-pixel-loop kernel only (rrt_kernel.hip); no proofs.
-constexpr int V_SKY = 5;
-constexpr int V_KERR_SKY = 6;
-// V_KERR_DISK: the general Kerr build with the accretion disk (rrt_set_disk).  It carries
-// the exit-mode march and takes the lensed sky's rule or the reference's at run time (kp.disk.lensed).
-// Per-pixel-loop kernel only; no proofs.
-constexpr int V_KERR_DISK = 7;
-// V_KERR_DISK_BB: V_KERR_DISK with the blackbody colour rule (RRT_DISK_BLACKBODY) in
-// place of the plain one: a build of its own, so that V_KERR_DISK keeps its registers and scratch.
-constexpr int V_KERR_DISK_BB = 8;
-// V_KERR_DISK_LIGHT / V_KERR_DISK_BB_LIGHT: the two disk builds with the disk importance-sampled as a
-// light (RRT_DISK_LIGHT; rrt_integrator.h disk_direct): builds of their own, so that
-// their parents keep their registers and scratch.  Everywhere else they behave as their parents.
-constexpr int V_KERR_DISK_LIGHT = 9;
-constexpr int V_KERR_DISK_BB_LIGHT = 10;
-// V_KERR_DISK_PT / V_KERR_DISK_PT_LIGHT: builds 8 and 10 with the Page-Thorne temperature profile
-// (RRT_DISK_PROFILE_PAGE_THORNE) as disk_rgb's q: builds of their own, so that the log
-// chain is no run-time branch in their parents.  Everywhere else they behave as their parents.
-constexpr int V_KERR_DISK_PT = 11;
-constexpr int V_KERR_DISK_PT_LIGHT = 12;
-__host__ __device__ constexpr bool is_lean(int v) { return v == 1 || v == 2; }
-__host__ __device__ constexpr bool is_sky(int v) { return v == V_SKY || v == V_KERR_SKY; }
-__host__ __device__ constexpr bool is_disk_pt(int v) { return v == V_KERR_DISK_PT || v == V_KERR_DISK_PT_LIGHT; }
-__host__ __device__ constexpr bool is_disk_light(int v) {
-  return v == V_KERR_DISK_LIGHT || v == V_KERR_DISK_BB_LIGHT || v == V_KERR_DISK_PT_LIGHT;
-}
-__host__ __device__ constexpr bool is_disk_bb(int v) { return v == V_KERR_DISK_BB || v == V_KERR_DISK_BB_LIGHT || is_disk_pt(v); }
-__host__ __device__ constexpr bool is_disk(int v) { return v == V_KERR_DISK || is_disk_bb(v) || is_disk_light(v); }
-__host__ __device__ constexpr bool is_kerr_build(int v) { return v == V_KERR || v == V_KERR_SKY || is_disk(v); }
-__host__ __device__ constexpr int general_of(int v) {  // non-LEAN build
-  return v == V_KERR || v == V_SW || is_sky(v) || is_disk(v) ? v : 0;
-}
 
 // ------------------------------------------------------------------ Kerr (build-defined)
 // The reference has no Kerr metric; this integrator is this build's design
@@ -1529,7 +1490,7 @@ __device__ __forceinline__ bool shadow_occluded_proof(const KParams& kp, v3 o, v
 // BVHAccel::intersect (bvh.cpp:103-113): march the geodesic as straight micro segments; the
 // incoming ray's min_t / max_t are dropped (camera clip planes and shadow-ray distance are
 // ignored, as in the reference).  Capture by the hole returns "no hit".  KERR: the Kerr build
-// of the kernel (kernel variant V_KERR, chosen by rrt_host.cpp launch() for a Kerr spacetime).
+// of the kernel (kernel variant V_KERR, chosen by rrt_host.cpp choose_variant for a Kerr spacetime).
 #if RRT_PROFILE
 #define RRT_QACC(v) do { if (ANY) cn.t_squery += clock64() - v; else cn.t_query += clock64() - v; } while (0)
 #else

@@ -27,13 +27,13 @@
 #include "rrt_internal.h"
 #include "rrt_scene_file.h"
 
-hipError_t rrt_launch_render(const KParams& kp, const KParams* d_kp, int deep, int count, int lean, int waves, uint32_t grid,
+hipError_t rrt_launch_render(const KParams& kp, const KParams* d_kp, int deep, int count, int variant, int waves, uint32_t grid,
                              hipStream_t stream);
-hipError_t rrt_launch_sample(const KParams& kp, const KParams* d_kp, int count, int lean, int waves, uint32_t grid, hipStream_t stream);
-hipError_t rrt_launch_batch(const KParams& kp, const KParams* d_kp, int lean, int waves, uint32_t grid, hipStream_t stream);
-hipError_t rrt_launch_first(const KParams& kp, const KParams* d_kp, int lean, int waves, uint32_t grid, hipStream_t stream);
+hipError_t rrt_launch_sample(const KParams& kp, const KParams* d_kp, int count, int variant, int waves, uint32_t grid, hipStream_t stream);
+hipError_t rrt_launch_batch(const KParams& kp, const KParams* d_kp, int variant, int waves, uint32_t grid, hipStream_t stream);
+hipError_t rrt_launch_first(const KParams& kp, const KParams* d_kp, int variant, int waves, uint32_t grid, hipStream_t stream);
 hipError_t rrt_launch_pixel_proof(const KParams* d_kp, uint32_t n_pixels, bool strips, hipStream_t stream);
-hipError_t rrt_launch_heavy(const KParams* d_kp, int lean, int waves, int nw, uint32_t grid, int drain, hipStream_t stream);
+hipError_t rrt_launch_heavy(const KParams* d_kp, int variant, int waves, int nw, uint32_t grid, int drain, hipStream_t stream);
 hipError_t rrt_launch_path(const KParams* d_kp, int waves, uint32_t grid, hipStream_t stream);
 hipError_t rrt_launch_env(const DEnv& env, uint64_t n, const double* dirs, float* rgb, hipStream_t stream);
 hipError_t rrt_launch_trace(const KParams* d_kp, const TraceArgs& a, int kerr, int any, int exit, int mode, int n_cu, int* mode_out,
@@ -140,7 +140,7 @@ struct rrt_ctx {
   size_t cont_cap = 0;
   uint32_t cont_seq = 0;      // the last launch's record tag (never 0)
   float* d_path_stack = nullptr;  // the path pool kernel's per-level terms (rrt_path.hip)
-  size_t path_stack_cap = 0;      // bytes
+  size_t path_stack_cap = 0;      // floats
   hipStream_t side = nullptr;  // the heavy pixels' kernel runs here, beside the batch kernel
   hipEvent_t ev_go = nullptr, ev_heavy = nullptr;
 #if RRT_PROFILE
@@ -211,7 +211,7 @@ struct rrt_ctx {
   KParams* d_kp = nullptr;  // the launch's parameters (kernels take them by pointer)
   uint32_t* d_counter = nullptr;
   uint32_t* d_tiles = nullptr;
-  size_t tiles_cap = 0;
+  size_t tiles_cap = 0;  // words (two a tile); every capacity below counts elements of its buffer
   uint32_t* d_order = nullptr;  // batch kernel: tile claim order
   size_t order_cap = 0;
   std::vector<uint32_t> h_order;  // what d_order holds
@@ -222,8 +222,8 @@ struct rrt_ctx {
   float* d_rgb = nullptr; int32_t* d_cnt = nullptr; uint32_t* d_draws = nullptr; uint32_t* d_ctr = nullptr;
   size_t px_cap = 0;
   // host-buffer ray queries (rrt_trace_rays / rrt_trace_camera): staging
-  void* d_trace_rays = nullptr; void* d_trace_hits = nullptr;
-  size_t trace_rays_cap = 0, trace_hits_cap = 0;  // bytes
+  rrt_ray* d_trace_rays = nullptr; rrt_hit* d_trace_hits = nullptr;
+  size_t trace_rays_cap = 0, trace_hits_cap = 0;
   float last_ms = 0.f, last_main_ms = 0.f;
   bool timed = false;
   uint32_t last_grid = 0;
@@ -1422,12 +1422,16 @@ extern "C" int rrt_partition_tiles(uint32_t fw, uint32_t fh, uint32_t ts, uint32
   return rrt_region_tiles(0, 0, fw, fh, ts, rank, world, out, max_tiles);
 }
 
-static int ensure(rrt_ctx* c, void** p, size_t& cap, size_t need, size_t elem) {
-  (void)cap;
-  if (need == 0) need = 1;
-  hipFree(*p);
-  *p = nullptr;
-  HIPCHK(c, hipMalloc(p, need * elem));
+// The context's device buffers only grow: afterwards p holds at least `need` elements; cap counts
+// elements of T too.  A regrow frees first, and hipFree waits for the device, so no earlier launch
+// still reads the old block.  zero: a new block starts cleared.
+template <class T>
+static int grow(rrt_ctx* c, T*& p, size_t& cap, size_t need, bool zero = false) {
+  if (cap >= need) return RRT_OK;
+  hipFree(p); p = nullptr; cap = 0;
+  HIPCHK(c, hipMalloc(&p, sizeof(T) * need));
+  if (zero) HIPCHK(c, hipMemset(p, 0, sizeof(T) * need));
+  cap = need;
   return RRT_OK;
 }
 
@@ -1443,6 +1447,10 @@ static int scratch_release(rrt_ctx* c, hipStream_t stream) {
   c->fenced = true;
   return RRT_OK;
 }
+struct FenceGuard {  // releases on every path out of its scope
+  rrt_ctx* c; hipStream_t s;
+  ~FenceGuard() { scratch_release(c, s); }
+};
 
 // The envelope the three proofs were validated in (tools/proof_sweep.py, profiles/
 // r03_proof_sweep.json: random holes inside and outside the room, cameras and resolutions, every
@@ -1520,46 +1528,10 @@ static void fill_scene_params(const rrt_ctx* c, uint32_t flags, KParams& kp) {
   }
 }
 
-static int launch(rrt_ctx* c, const rrt_render_params* p, const uint32_t* tiles, uint32_t n_tiles, uint32_t ts,
-                  uint32_t cx0, uint32_t cy0, uint32_t cx1, uint32_t cy1, float* d_rgb, int32_t* d_cnt,
-                  uint32_t* d_draws, uint32_t* d_ctr, hipStream_t stream) {
-  if (!c->has_scene) return fail(c, RRT_E_INVALID, "no scene (rrt_set_scene)");
-  if (!c->has_camera) return fail(c, RRT_E_INVALID, "no camera (rrt_set_camera)");
-  if (int rc = check_disk(c)) return rc;  // before any device work
-  if (c->device < 0) return fail(c, RRT_E_NO_DEVICE, "host-only context cannot render");
-  if (p->frame_w == 0 || p->frame_h == 0) return fail(c, RRT_E_INVALID, "frame size is zero");
-  if (p->samples_per_batch == 0) return fail(c, RRT_E_INVALID, "samples_per_batch must be > 0");
-  if (p->max_ray_depth > RRT_MAX_DEPTH) return fail(c, RRT_E_INVALID, "max_ray_depth > 16 not supported");
-  if (ts == 0 || ts % 8 != 0) return fail(c, RRT_E_INVALID, "tile_size must be a positive multiple of 8");
-  if (n_tiles == 0) return RRT_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (int rc = scratch_acquire(c, stream)) return rc;
-  // whatever path leaves this function, the work already enqueued on `stream` fences the
-  // workspace for the next user on another stream
-  struct FenceGuard {
-    rrt_ctx* c; hipStream_t s;
-    ~FenceGuard() { scratch_release(c, s); }
-  } fence_guard{c, stream};
-  // once the heavy pixels' kernel is forked onto the side stream, every path out of here joins it
-  // into `stream` first (so the fence above covers its reads of d_kp / d_counter / the heavy list):
-  // 1 = launched, 2 = its completion event recorded, 3 = joined
-  struct JoinGuard {
-    rrt_ctx* c; hipStream_t s; hipStream_t fork; hipEvent_t done; int state;
-    ~JoinGuard() {
-      if (state == 1) (void)hipStreamSynchronize(fork);
-      else if (state == 2) (void)hipStreamWaitEvent(s, done, 0);
-    }
-  } join_guard{c, stream, c->side, c->ev_heavy, 0};
-  if (c->tiles_cap < n_tiles) {
-    // hipFree waits for the device, so no launch still reads the old list
-    hipFree(c->d_tiles); c->d_tiles = nullptr;
-    HIPCHK(c, hipMalloc(&c->d_tiles, sizeof(uint32_t) * 2 * n_tiles));
-    c->tiles_cap = n_tiles;
-  }
-  HIPCHK(c, hipMemcpyAsync(c->d_tiles, tiles, sizeof(uint32_t) * 2 * n_tiles, hipMemcpyHostToDevice, stream));
-  HIPCHK(c, hipMemsetAsync(c->d_counter, 0, kCounterBytes, stream));
-  KParams kp{};
-  fill_scene_params(c, p->flags, kp);
+// The constants of the three proofs (camera-ray miss, shadow-ray occlusion, Kerr occlusion) and each
+// one's switch.  Call with kp.hole filled (fill_scene_params).  Returns whether the launch lies in the
+// envelope the Schwarzschild proofs (and the pixel miss proof pass) hold in.
+static bool fill_proof_params(const rrt_ctx* c, uint32_t flags, KParams& kp) {
   bool proofs_valid = false;
   {  // camera-ray miss proof constants (rrt_device.h camera_miss_proof)
     const DHole& h = kp.hole;
@@ -1591,7 +1563,7 @@ static int launch(rrt_ctx* c, const rrt_render_params* p, const uint32_t* tiles,
     // share these constants, and each has its own switch below
     proofs_valid = h.kind == RRT_METRIC_SCHWARZSCHILD && fin && h.dt > 0.0 && h.dt < 3.0 && h.sin_dt > 0.0 &&
                    h.steps >= 1 && in_proof_envelope(c);
-    mp.on = (proofs_valid && !(p->flags & RRT_RENDER_NO_MISS_PROOF)) ? 1u : 0u;
+    mp.on = (proofs_valid && !(flags & RRT_RENDER_NO_MISS_PROOF)) ? 1u : 0u;
   }
   {  // shadow-ray occlusion proof: the same recurrence, against the root box's face triangles
     kp.occ = c->occ;
@@ -1607,7 +1579,7 @@ static int launch(rrt_ctx* c, const rrt_render_params* p, const uint32_t* tiles,
     }
     // the point-light scenes' builds carry no proof (rrt_sample.hip RRT_OCC_TAG); off for them in
     // every kernel, so the counting passes count what their batch kernel executes
-    kp.occ.on = (proofs_valid && any && fin && c->lean != 2 && !(p->flags & RRT_RENDER_NO_SHADOW_PROOF)) ? 1u : 0u;
+    kp.occ.on = (proofs_valid && any && fin && c->lean != 2 && !(flags & RRT_RENDER_NO_SHADOW_PROOF)) ? 1u : 0u;
     // Kerr shadow rays (rrt_device.h kerr_occluded_proof): the same face triangles
     // against a coarse march, inside the envelope its margin was swept over
     // (tools/kerr_proof_sweep.py -> profiles/r04_kerr_proof_sweep.json)
@@ -1628,7 +1600,7 @@ static int launch(rrt_ctx* c, const rrt_render_params* p, const uint32_t* tiles,
     const bool kenv = h.kind == RRT_METRIC_KERR && any && fin && kin && h.m > 0.0 && h.dt >= RRT_KPROOF_DT_MIN &&
                       h.dt <= RRT_KPROOF_DT_MAX && h.a <= RRT_KPROOF_SPIN_MAX * h.m &&
                       h.r_esc2 <= (RRT_KPROOF_REACH_M * h.m) * (RRT_KPROOF_REACH_M * h.m);
-    if (kenv && !(p->flags & RRT_RENDER_NO_SHADOW_PROOF)) {
+    if (kenv && !(flags & RRT_RENDER_NO_SHADOW_PROOF)) {
       kq.stretch = RRT_KPROOF_STRETCH;
       kq.r_near2 = (RRT_KPROOF_NEAR_M * h.m) * (RRT_KPROOF_NEAR_M * h.m);
       kq.delta = RRT_KPROOF_DELTA_M * h.m;
@@ -1644,6 +1616,560 @@ static int launch(rrt_ctx* c, const rrt_render_params* p, const uint32_t* tiles,
       }
     }
   }
+  return proofs_valid;
+}
+
+// ---------------------------------------------------------------- render launches
+// Every render (rrt_render, rrt_render_tiles_device, the group renders) goes through launch(), in
+// stages: check_launch (every refusal; no device) -> fill_scene_params / fill_proof_params /
+// fill_disk_params (the kernels' constants) -> plan_launch (every decision; no HIP call, no write to
+// the context) -> enqueue (the only stage that touches buffers and streams).
+
+// What a call asks for, from its flags and the spacetime in force: shared by the checks and the plan.
+struct LaunchMode {
+  bool deep, count;  // bounce paths (max_ray_depth >= 2); a counting launch (RRT_RENDER_COUNTERS with a counter buffer)
+  bool kerr, sw;     // the Kerr march; the reference's compile-time switches (RRT_RENDER_THIN_LENS .. RRT_RENDER_ILLUM_MASK)
+  bool sky, disk;    // the lensed sky (RRT_SPACETIME_LENSED_SKY); the accretion disk (rrt_set_disk, §12)
+  bool path_pool;    // RRT_RENDER_WAVEFRONT
+};
+static LaunchMode launch_mode(const rrt_ctx* c, const rrt_render_params* p, bool has_counters) {
+  return LaunchMode{p->max_ray_depth >= 2, (p->flags & RRT_RENDER_COUNTERS) && has_counters, c->hole.kind == RRT_METRIC_KERR,
+                    ((p->flags >> 22) & 63u) != 0, c->lensed_sky, c->has_disk, (p->flags & RRT_RENDER_WAVEFRONT) != 0};
+}
+
+// Every refusal of a render launch, before any device work: no HIP call.  The order is part of the
+// behaviour (a call with two faults reports the first).  kLaunchEmpty: nothing to render, not a failure.
+constexpr int kLaunchEmpty = 1;
+static int check_launch(rrt_ctx* c, const rrt_render_params* p, const LaunchMode& m, uint32_t n_tiles, uint32_t ts) {
+  if (!c->has_scene) return fail(c, RRT_E_INVALID, "no scene (rrt_set_scene)");
+  if (!c->has_camera) return fail(c, RRT_E_INVALID, "no camera (rrt_set_camera)");
+  if (int rc = check_disk(c)) return rc;  // fill_disk_params' failures
+  if (c->device < 0) return fail(c, RRT_E_NO_DEVICE, "host-only context cannot render");
+  if (p->frame_w == 0 || p->frame_h == 0) return fail(c, RRT_E_INVALID, "frame size is zero");
+  if (p->samples_per_batch == 0) return fail(c, RRT_E_INVALID, "samples_per_batch must be > 0");
+  if (p->max_ray_depth > RRT_MAX_DEPTH) return fail(c, RRT_E_INVALID, "max_ray_depth > 16 not supported");
+  if (ts == 0 || ts % 8 != 0) return fail(c, RRT_E_INVALID, "tile_size must be a positive multiple of 8");
+  if (n_tiles == 0) return kLaunchEmpty;
+  if (m.sw && m.kerr) return fail(c, RRT_E_INVALID, "the reference's switches (THIN_LENS, ADAPTIVE, ILLUM, ENV_HEMI, "
+                                                    "MICROFACET_HEMI) are built for the Schwarzschild stepper only");
+  if (m.sw && ((((p->flags >> 22) & 63u) >> 4) ^ 2u) == 3u && p->max_ray_depth == 0)
+    return fail(c, RRT_E_INVALID, "ILLUM 3 with max_ray_depth 0: the reference's recursion depth is unbounded there "
+                                  "(Ray::depth is size_t and wraps below 0; only Russian roulette ends it), beyond "
+                                  "RRT_MAX_DEPTH");
+  // the lensed sky and the accretion disk have general per-pixel-loop builds only (rrt_kernel.hip): every
+  // query the exit-mode march, no proof
+  const char* only_loop = m.sky ? "the lensed sky (RRT_SPACETIME_LENSED_SKY)" : m.disk ? "the accretion disk (rrt_set_disk)" : nullptr;
+  if (only_loop && (m.sw || (p->flags & (RRT_RENDER_WAVEFRONT | RRT_RENDER_DEEP_SAMPLE | RRT_RENDER_COUNTERS))))
+    return fail(c, RRT_E_INVALID, std::string(only_loop) + " renders in the per-pixel-loop kernel only: not with "
+                                  "RRT_RENDER_WAVEFRONT, RRT_RENDER_DEEP_SAMPLE, RRT_RENDER_COUNTERS or the reference's "
+                                  "switch flags");
+  // the path pool kernel (rrt_path.hip): its path records pack the pixel as x | y << 16, and its
+  // light-sample cursor holds 11 bits: n_lights x ns_area_light < 2048
+  if (m.path_pool && (p->frame_w > 65535u || p->frame_h > 65535u))
+    return fail(c, RRT_E_INVALID, "RRT_RENDER_WAVEFRONT (the path pool kernel) renders frames of at most 65535 pixels a side");
+  if (m.path_pool && !(m.deep && !m.count && !m.kerr && !m.sw && p->ns_aa >= 1 &&
+                       (uint64_t)all_lights(c).size() * std::max<uint32_t>(1u, p->ns_area_light) < 2048u))
+    return fail(c, RRT_E_INVALID, "RRT_RENDER_WAVEFRONT (the path pool kernel) renders max_ray_depth >= 2 "
+                                  "Schwarzschild frames without counters or switches, n_lights x ns_area_light < 2048");
+  return RRT_OK;
+}
+
+// The kernel build of a launch.  LEAN builds when the scene allows them (no environment map,
+// importance-sampled direct light) and the launch is a plain depth <= 1 one.
+static int choose_variant(const rrt_ctx* c, const rrt_render_params* p, const LaunchMode& m, const DDisk& d) {
+  if (m.disk) {
+    if (d.blackbody && d.profile == RRT_DISK_PROFILE_PAGE_THORNE)
+      return d.light ? rrt::V_KERR_DISK_PT_LIGHT : rrt::V_KERR_DISK_PT;
+    if (d.light) return d.blackbody ? rrt::V_KERR_DISK_BB_LIGHT : rrt::V_KERR_DISK_LIGHT;
+    return d.blackbody ? rrt::V_KERR_DISK_BB : rrt::V_KERR_DISK;
+  }
+  if (m.sky) return m.kerr ? rrt::V_KERR_SKY : rrt::V_SKY;
+  if (m.kerr) return rrt::V_KERR;
+  if (m.sw) return rrt::V_SW;
+  return (!m.deep && !m.count && !c->env_w && !p->direct_hemisphere) ? c->lean : rrt::V_GENERAL;
+}
+
+enum class Family { Batch, PathPool, PixelLoop, PerSample };
+
+// Every decision of a launch.  The *_n fields and the two capacities are the element counts of the
+// workspace buffers the launch needs; 0: that buffer, and the pass or list it serves, is off.
+struct LaunchPlan {
+  Family family;
+  int variant;  // the kernel build (rrt_internal.h V_*)
+  int deep, count;
+  bool deep_sample;  // the per-sample refill kernel for bounce paths
+  bool deep_list;    // bounce paths behind the pixel miss proof pass
+  int waves;         // register budget asked for, waves per SIMD (every family but the batch one)
+  int batch_w, first_w, heavy_w;  // the batch kernel's, its pre-pass's and the heavy kernel's
+  uint32_t grid;     // the main kernel's blocks, before the batch grid leaves room for the heavy kernel
+  uint32_t bgrid;    // the batch kernel's blocks
+  uint32_t first_grid;
+  uint32_t n_pixels;  // pixel slots of the tile list (0: a family that claims 8 x 8 blocks)
+  uint32_t n_queues, n_sectors;  // claim counters; 45-degree sectors of the claim order (per-XCD queues)
+  bool stripe, ordered;
+  size_t order_n, first_n, list_n, strip_n, path_stack_n;  // tile order, sample 0, claim list, strip list, path stack
+  uint32_t heavy_cap, cont_cap;  // heavy list; continuation records
+  int heavy_nw;      // waves per heavy pixel
+  uint32_t heavy_grid;
+};
+
+// The A/B knobs of a launch: the bit fields of rrt_render_params.variant and the RRT_AB_* environment,
+// read at every launch (tests change the environment between launches of one process)
+struct AbKnobs {
+  uint32_t waves;     // bits 0..7: register budget, waves per SIMD
+  uint32_t first_w;   // 8..11: the pre-pass's (default 3)
+  uint32_t room;      // 12..15: round 3's fixed room, of room - 1 blocks per CU beyond the heavy waves
+  uint32_t near;      // 16..19: the heavy pixels' radius; 1: capture-boundary pixels only, 2 .. 6: 1.1 / 1.5 / 2.0 / 3.0 / 5.0
+  uint32_t heavy_nw;  // 20..21: waves per heavy pixel; 1 / 2 / 3: 1 (2 for the point-light build) / 4 / 2
+  bool claim_fwd;     // 22: the pixel proof pass's claim order
+  bool no_room;       // 23: leave the batch grid as it is
+  uint32_t heavy_w;   // 24..27: the heavy kernel's register budget
+  uint32_t heavy_g;   // 28..31: heavy waves per CU (default 2)
+  const char *cont, *cont_min, *cont_room, *cont_waiters, *prio_ticks;  // RRT_AB_CONT .. RRT_AB_PRIO_TICKS
+  static uint32_t u32(const char* s, uint32_t dflt) { return s ? (uint32_t)std::strtoul(s, nullptr, 10) : dflt; }
+};
+static AbKnobs read_ab_knobs(uint32_t v) {
+  return AbKnobs{v & 0xffu, (v >> 8) & 0xfu, (v >> 12) & 0xfu, (v >> 16) & 0xfu, (v >> 20) & 3u, ((v >> 22) & 1u) != 0,
+                 ((v >> 23) & 1u) != 0, (v >> 24) & 0xfu, (v >> 28) & 0xfu, std::getenv("RRT_AB_CONT"),
+                 std::getenv("RRT_AB_CONT_MIN"), std::getenv("RRT_AB_CONT_ROOM"), std::getenv("RRT_AB_CONT_WAITERS"),
+                 std::getenv("RRT_AB_PRIO_TICKS")};
+}
+
+// the RNG draws of one camera sample that hits, at depth <= 1: jitter + the direct-lighting samplers
+static uint32_t draws_per_hit(const rrt_ctx* c, const rrt_render_params* p) {
+  uint32_t dh = 2;
+  if (p->max_ray_depth >= 1) {
+    if (p->direct_hemisphere) {
+      dh += 2u * (uint32_t)all_lights(c).size() * p->ns_area_light;
+    } else {
+      for (const DLight& l : all_lights(c)) {
+        const uint32_t num = l.is_delta ? 1u : p->ns_area_light;
+        // area, hemisphere and environment samplers draw 2 each; point / directional none
+        const bool sampled = l.type == RRT_LIGHT_AREA || l.type == RRT_LIGHT_HEMISPHERE || l.type == 5u;
+        dh += sampled ? 2u * num : 0u;
+      }
+    }
+  }
+  return dh;
+}
+
+// The batch family's part of the plan: queues, pre-pass, pixel miss proof pass, heavy pixels, continuations.
+static void plan_batch(const rrt_ctx* c, const rrt_render_params* p, const AbKnobs& ab, bool proofs_valid, bool zero_stops,
+                       LaunchPlan& pl, KParams& kp) {
+  const uint32_t flags = p->flags;
+  const bool lean_build = rrt::is_lean(pl.variant);
+  kp.draws_miss = 2;
+  kp.draws_hit = draws_per_hit(c, p);
+  uint32_t gsz = 8;  // groups of 8..32 lanes (GroupLds holds 32 groups per block)
+  const uint32_t want_g = std::min<uint32_t>(std::min<uint32_t>(p->ns_aa, p->samples_per_batch), 32u);
+  while (gsz < want_g) gsz <<= 1;
+  kp.group = gsz;
+  // One queue per XCD (workgroups are dealt to the 8 XCDs round-robin, so block b starts on
+  // queue b % 8): queue q holds the tiles of the q-th 45-degree sector about the frame centre,
+  // centre-first.  Each XCD's L2 then serves a coherent wedge of the frame (a narrower slice
+  // of the BVH), every wedge gets its share of the costly centre, and a block whose queue is
+  // empty moves on to the next queue, so the load still balances at pixel granularity.
+  pl.ordered = flags & RRT_RENDER_ORDERED;
+  // A/B (profiles/r01_queues_ab.md): per-XCD queues cost the LEAN cfg3 build 6% and save the
+  // Kerr cfg5 build 2%, so they are the default for the general / Kerr builds only
+  const bool xcd_q = (flags & RRT_RENDER_XCD_QUEUES) ||
+                     (!lean_build && !(flags & RRT_RENDER_ONE_QUEUE) && !(flags & RRT_RENDER_STRIPED_QUEUES));
+  // Striped queues (the LEAN default): the centre-first order dealt round-robin over one
+  // counter per XCD, so the claim atomics spread over 8 addresses while the order stays global
+  pl.stripe = !pl.ordered && !(flags & RRT_RENDER_ONE_QUEUE) && !(flags & RRT_RENDER_XCD_QUEUES) &&
+              ((flags & RRT_RENDER_STRIPED_QUEUES) || lean_build);
+  pl.n_queues = (pl.ordered || !(xcd_q || pl.stripe)) ? 1u : RRT_MAX_QUEUES;
+  pl.n_sectors = pl.stripe ? 1u : pl.n_queues;
+  // sample-0 pre-pass: off by default (with the slot speculation a wrong first hypothesis
+  // costs one round, less than the extra pass; tools/ab_kernels.py cfg3 46.4 vs 47.8 ms)
+  if ((flags & RRT_RENDER_PREPASS) && !(flags & RRT_RENDER_NO_FIRST)) pl.first_n = pl.n_pixels;
+  // pixel miss proof pass (rrt_pixel_proof_kernel): the area/point-light builds, whose misses
+  // are black, with a claim order it can compact (striped or one queue); list entries keep bit
+  // 31 for the first-hypothesis hint
+  if (!(lean_build && proofs_valid && zero_stops && !c->env_w && !pl.first_n && (pl.stripe || pl.n_queues == 1) &&
+        pl.n_pixels < 0x80000000u && !(flags & RRT_RENDER_NO_PIXEL_PROOF)))
+    return;
+  pl.list_n = pl.n_pixels;
+  kp.claim_back = ab.claim_fwd ? 0u : 1u;  // hit-first claim order (rrt_pixel_proof_kernel)
+  // Heavy pixels (rrt_device.h pixel_heavy): the pass lists them apart and rrt_heavy_kernel
+  // renders them slot-parallel, a block of waves per pixel (rrt_sample.hip
+  // heavy_pixel_block); needs a hit to take a whole number of slots (Dh = k Dm)
+  // Where the heavy pixels' latency bounds the launch: launches covering at most 60% of the
+  // frame (one rank's tiles of a multi-GPU frame, the regions of the host path; cfg3 split 8
+  // ways, slowest rank 8.1 -> 4.4 ms), and pixels of 4 or more adaptive steps, whose chains of
+  // rounds outlast the frame (cfg4, 256 spp: 16.5 -> 15.0 ms).  A whole cfg3 frame (2 steps a
+  // pixel) is bound by its throughput, and the heavy kernel's room in the batch grid costs more
+  // than it saves (18.3 -> 19.0 ms).
+  const uint64_t frame_px = (uint64_t)p->frame_w * p->frame_h;
+  const bool part = (uint64_t)pl.n_pixels * 5u <= frame_px * 3u;
+  const bool share_ok = (flags & RRT_RENDER_HEAVY) || part || p->ns_aa >= 4u * p->samples_per_batch;
+  if ((flags & RRT_RENDER_NO_HEAVY) || !share_ok || !(c->hole.r > 0.0) || kp.draws_hit % kp.draws_miss != 0) return;
+  // at most 1/256 of the pixels (4096 at least): a frame mostly near the hole stays with
+  // the batch kernel, whose rounds cost less than 64 slots a step for unmixed pixels
+  pl.heavy_cap = std::min<uint32_t>(pl.n_pixels, std::max<uint32_t>(4096u, pl.n_pixels / 256u));
+  const uint32_t nv = ab.near;
+  const double near = nv == 1 ? 0.0 : nv == 2 ? 1.1 : nv == 3 ? 1.5 : nv == 4 ? 2.0 : nv == 5 ? 3.0 : nv == 6 ? 5.0 : RRT_HEAVY_NEAR;
+  kp.heavy_r2 = (near * c->hole.r) * (near * c->hole.r);
+  // Continuations (rrt_sample.hip cont_push): in launches of at most 60% of the
+  // frame (a rank's share), pixels of three or more adaptive steps go to waiting heavy blocks
+  // after a check with two or more steps to go (cfg4, 256 spp: the 8-way split's ranks ended
+  // on a few 8-step pixels, one step a round on the group path; profiles/r06_cont_w8_cfg4.txt).
+  // A whole frame keeps them on the group path (its waiting heavy blocks cost ~2%).
+  // A/B (AbKnobs): RRT_AB_CONT=0 off / 1 on for any launch; _MIN samples left; _ROOM batch blocks of room; _WAITERS heavy blocks that wait
+  if (!(p->ns_aa >= 3u * p->samples_per_batch && (ab.cont ? ab.cont[0] == '1' : part))) return;
+  pl.cont_cap = std::min<uint32_t>(pl.n_pixels, std::max<uint32_t>(4096u, pl.n_pixels / 256u));
+  kp.cont_min_left = AbKnobs::u32(ab.cont_min, 2u * p->samples_per_batch);
+  // room for 32 heavy blocks from the launch's start (a rank's first pixels are its centre's,
+  // the costliest: their first checks come early)
+  kp.cont_room = AbKnobs::u32(ab.cont_room, part ? 32u : 0u);
+  kp.cont_ticks = 5000000u;  // 50 ms of wall clock (100 MHz)
+  kp.cont_waiters = AbKnobs::u32(ab.cont_waiters, ~0u);
+}
+
+// The batch family's geometry: the register budgets, the heavy kernel's blocks and the room the batch grid
+// (pl.bgrid, from pl.grid) leaves for them.
+static void plan_batch_grid(const rrt_ctx* c, const AbKnobs& ab, LaunchPlan& pl, KParams& kp) {
+  const uint32_t n_cu = (uint32_t)c->n_cu;
+  pl.first_w = (pl.variant == rrt::V_LEAN && (ab.first_w == 4 || ab.first_w == 5)) ? (int)ab.first_w : 3;
+  pl.first_grid = std::min<uint32_t>((pl.n_pixels + 255) / 256, n_cu * 8u);
+  // the heavy pixels' kernel (batch launches with a heavy list); waves per heavy pixel: 2 (a 64-sample
+  // pixel's two steps in one round), 4 with continuations (256 slots a round: the rest of a 256-sample pixel)
+  pl.heavy_nw = ab.heavy_nw == 0 ? (pl.cont_cap ? 4 : 2) : ab.heavy_nw == 1 ? (pl.variant == rrt::V_LEAN_POINT ? 2 : 1) : ab.heavy_nw == 2 ? 4 : 2;
+  // heavy waves: ab.heavy_g x the CU count (default 2), in blocks of heavy_nw waves
+  const uint32_t heavy_waves = std::min<uint32_t>(n_cu * (ab.heavy_g ? ab.heavy_g : 2u), n_cu * 4u);
+  pl.heavy_grid = std::max<uint32_t>(1u, heavy_waves / (uint32_t)pl.heavy_nw);
+  pl.heavy_w = ab.heavy_w == 5 ? 5 : 4;
+  const bool static_room = ab.room != 0u;
+  if (pl.heavy_cap && !ab.no_room && !static_room) {  // the batch kernel sizes the heavy kernel's room on the device
+    kp.heavy_grid = pl.heavy_grid;
+    kp.heavy_nw = (uint32_t)pl.heavy_nw;
+  }
+  // the batch kernel's waves/SIMD: the area-light build at 4 (cfg3 15.71 -> 15.33 ms, cfg2 10.33 -> 10.01 ms
+  // against 5, since the search tree took the local oversized leaves), the point-light build at 5 (cfg4
+  // 14.15 ms against 14.65 at 4) -- profiles/r03_heavy_ab.md; general / Kerr builds: 3 by default
+  // (cfg5: 4.56 s at 2 waves, 3.37 s at 3)
+  const int w25 = (ab.waves >= 2 && ab.waves <= 5) ? (int)ab.waves : 0;
+  pl.batch_w = pl.variant == rrt::V_LEAN ? (w25 ? w25 : 4) : pl.variant == rrt::V_LEAN_POINT ? (ab.waves >= 3 && ab.waves <= 5 ? (int)ab.waves : 5) : (w25 ? w25 : 3);
+  if (pl.heavy_cap) {
+    // the batch grid leaves room for the heavy kernel's blocks (one per CU at most, <= 128 VGPRs
+    // and 25 KB of LDS next to four batch blocks), whichever kernel the hardware dispatches first
+    const uint32_t resident = n_cu * (uint32_t)pl.batch_w;  // blocks of 4 waves
+    const uint32_t spare = (static_room ? ab.room - 1u : 0u) * n_cu + (heavy_waves + 3u) / 4u;  // room, in batch blocks
+    if (static_room) {
+      if (!ab.no_room && pl.bgrid + spare > resident) pl.bgrid = resident > spare ? resident - spare : 1u;
+    } else if (!ab.no_room) {
+      // room sized on the device to the heavy pixels the pass found (rrt_batch_kernel prologue,
+      // kp.heavy_grid / heavy_nw): the grid is exactly the resident blocks, so a block that
+      // leaves frees a slot no pending batch block can take
+      pl.bgrid = std::min(pl.bgrid, resident);
+    }
+  }
+}
+
+// Every decision of a launch, from its flags, the A/B knobs and the context's scene and device: the plan,
+// and in kp the constants that state it to the kernels.  No HIP call and no write to the context.
+static LaunchPlan plan_launch(const rrt_ctx* c, const rrt_render_params* p, const LaunchMode& m, bool proofs_valid,
+                              uint32_t n_tiles, uint32_t ts, KParams& kp) {
+  LaunchPlan pl{};
+  const uint32_t flags = p->flags, n_cu = (uint32_t)c->n_cu;
+  const AbKnobs ab = read_ab_knobs(p->variant);
+  const uint32_t wv = ab.waves;
+  pl.deep = m.deep ? 1 : 0;
+  pl.count = m.count ? 1 : 0;
+  // bounce paths (depth >= 2): the per-pixel-loop kernel by default; RRT_RENDER_DEEP_SAMPLE selects
+  // the per-sample refill kernel (rrt_sample.hip, one lane per pixel, a lane whose pixel is done
+  // takes the next at the next sample boundary) -- m3 A/B, profiles/r03_ab_deep.jsonl: 177 ms
+  // pixel loop vs 236 ms refill at 3 waves/SIMD, identical outputs
+  pl.deep_sample = m.deep && !m.count && !m.kerr && !m.sw && (flags & RRT_RENDER_DEEP_SAMPLE) && !(flags & RRT_RENDER_PIXEL_LOOP);
+  // Kernel family.  Depth <= 1: the per-sample kernel (rrt_sample.hip), and its sample-parallel batch
+  // kernel whenever a pixel takes more than one sample (it needs each camera sample's RNG draw count to
+  // depend only on whether its query hit, which holds at depth <= 1); RRT_RENDER_PIXEL_LOOP selects the
+  // general per-pixel-loop kernel (rrt_kernel.hip), which also renders depth >= 2, the switches, the
+  // lensed sky and the disk.  RRT_RENDER_WAVEFRONT: the bounce paths in the path pool kernel
+  // (rrt_path.hip: one ray per lane per round, the paths' integrator state between rays in LDS), an A/B
+  // variant: m3 269 ms at 3 waves/SIMD vs 172 ms for the per-pixel loop.
+  const bool pixel_loop = !m.path_pool && ((m.deep && !pl.deep_sample) || (flags & RRT_RENDER_PIXEL_LOOP) || m.sw || m.sky || m.disk);
+  const bool batch = !m.deep && !m.count && !pixel_loop && std::min(p->ns_aa, p->samples_per_batch) >= 5 &&
+                     !(flags & RRT_RENDER_PER_PIXEL);
+  pl.family = batch ? Family::Batch : m.path_pool ? Family::PathPool : pixel_loop ? Family::PixelLoop : Family::PerSample;
+  pl.variant = choose_variant(c, p, m, kp.disk);
+  // bounce builds: 3 waves/SIMD (m3 A/B, profiles/r03_ab_deep.jsonl: 363 / 263 / 180 / 180 ms at 1 / 2 / 3 / 4)
+  pl.waves = (wv >= 1 && wv <= 6) ? (int)wv : m.path_pool ? RRT_PATH_WAVES : m.deep ? 3 : (pixel_loop ? 2 : 3);
+  // The pixel miss proof pass writes a proven pixel's result as the first adaptive check's stop on
+  // all-zero samples, which holds only when 1.96 * 0 <= max_tolerance * 0 (a finite tolerance; with an
+  // infinite or NaN one the reference runs all ns_aa samples, part1_code.cpp:147-158)
+  const bool zero_stops = 0.0 <= (double)p->max_tolerance * 0.0 && p->samples_per_batch >= 2;
+  // The bounce (depth >= 2) per-pixel-loop kernel behind the pass: a proven pixel's samples all miss at
+  // any depth (est_radiance returns the black miss, 2 draws each), so the pass writes it and the kernel
+  // claims only the listed pixels, 64 per wave, in a centre-first order.  The path pool kernel claims
+  // from the same centre-first order, listed or not.
+  pl.deep_list = m.deep && !m.count && !m.sw && proofs_valid && !c->env_w && !m.kerr && kp.miss.on && zero_stops &&
+                 !(flags & RRT_RENDER_NO_PIXEL_PROOF);
+  if (batch || pl.deep_list || m.path_pool) {
+    pl.n_pixels = n_tiles * ts * ts;
+    pl.order_n = n_tiles;
+  }
+  if (batch) {
+    plan_batch(c, p, ab, proofs_valid, zero_stops, pl, kp);
+  } else if (pl.deep_list || m.path_pool) {
+    kp.draws_miss = 2;
+    pl.ordered = flags & RRT_RENDER_ORDERED;
+    pl.n_sectors = 1;
+    if (pl.deep_list) pl.list_n = pl.n_pixels;
+  }
+  // the pass's strip level: tiles whose rows split into strips of 64 claim indices (ts | 64 or 64 | ts)
+  if (pl.list_n && pl.n_pixels >= 64u) pl.strip_n = pl.n_pixels / 64u;
+  // persistent grid, 4 waves per block, up to 8 blocks per CU (the 32-wave limit): as many
+  // blocks as the kernel's registers allow become resident; any others start when a resident
+  // block exits and find the atomic work counter exhausted
+  const uint32_t want = batch ? (uint32_t)(((uint64_t)pl.n_pixels * kp.group + 255) / 256) : (kp.n_blocks + 3) / 4;
+  pl.grid = std::min<uint32_t>(want, n_cu * 8u);
+  if (m.path_pool) {  // 256 paths a block, the resident blocks only (each path holds a stack slot)
+    const uint32_t pw = (pl.waves >= 2 && pl.waves <= 4) ? (uint32_t)pl.waves : (uint32_t)RRT_PATH_WAVES;
+    pl.grid = std::max<uint32_t>(1u, std::min<uint32_t>((pl.n_pixels + 255u) / 256u, n_cu * pw));
+    // levels 0 .. max_ray_depth - 1 of the recursion, then each path's pixel record
+    pl.path_stack_n = (size_t)RRT_PATH_FIELDS * ((size_t)p->max_ray_depth + 1u) * pl.grid * 256u;
+  }
+  if (pl.grid == 0) pl.grid = 1;
+  pl.bgrid = pl.grid;
+  if (batch) plan_batch_grid(c, ab, pl, kp);
+  // tail priority threshold (A/B: RRT_AB_PRIO_TICKS in the environment)
+  kp.prio_ticks = AbKnobs::u32(ab.prio_ticks, 50000u);
+  kp.n_pixels = pl.n_pixels;
+  kp.n_queues = batch ? pl.n_queues : 0u;
+  kp.q_stripe = pl.stripe ? 1u : 0u;
+  kp.heavy_cap = pl.heavy_cap;
+  // (the heavy kernel's continuation wait ends when all kp.batch_waves batch waves have exited)
+  kp.batch_waves = pl.bgrid * 4u;
+  return pl;
+}
+
+// The claim order of a tile list: the tiles nearest the frame centre first (where the geometry and
+// the black hole's ring usually are), so the launch ends on cheap border tiles rather than on a
+// costly region; consecutive claims stay spatially adjacent (coherent waves, warm caches).  With
+// n_sectors > 1 the tiles of each 2 pi / n_sectors sector about the centre first, centre-first within
+// it: end[q] is the number of tiles up to and including sector q's.  ordered: the list's own order.
+struct ClaimOrder {
+  std::vector<uint32_t> order;
+  uint32_t end[RRT_MAX_QUEUES];
+};
+static ClaimOrder claim_order(const uint32_t* tiles, uint32_t n_tiles, uint32_t ts, uint32_t frame_w, uint32_t frame_h,
+                              uint32_t n_sectors, bool ordered) {
+  ClaimOrder co;
+  co.order.resize(n_tiles);
+  for (uint32_t k = 0; k < n_tiles; ++k) co.order[k] = k;
+  std::vector<uint32_t> sector(n_tiles, 0);
+  if (!ordered) {
+    const double cx = 0.5 * frame_w, cy = 0.5 * frame_h;
+    std::vector<double> key(n_tiles);
+    for (uint32_t k = 0; k < n_tiles; ++k) {
+      const double dx = tiles[2 * k] + 0.5 * ts - cx, dy = tiles[2 * k + 1] + 0.5 * ts - cy;
+      key[k] = dx * dx + dy * dy;
+      if (n_sectors > 1) {
+        const double a = std::atan2(dy, dx) + kPI;  // [0, 2 pi]
+        sector[k] = std::min<uint32_t>((uint32_t)(a * (n_sectors / (2 * kPI))), n_sectors - 1);
+      }
+    }
+    std::stable_sort(co.order.begin(), co.order.end(), [&](uint32_t a, uint32_t b) {
+      return sector[a] != sector[b] ? sector[a] < sector[b] : key[a] < key[b];
+    });
+  }
+  for (uint32_t q = 0, k = 0; q < RRT_MAX_QUEUES; ++q) {
+    while (k < n_tiles && sector[co.order[k]] == q) ++k;
+    co.end[q] = q + 1 < n_sectors ? k : n_tiles;
+  }
+  return co;
+}
+
+// the kernel name of rrt_stats.kernel; the waves printed are the ones asked for, which a shim may replace
+static std::string kernel_name(const LaunchPlan& pl, const LaunchMode& m) {
+  const char* tf[2] = {"false", "true"};
+  const char* pass = pl.list_n ? "rrt_pixel_proof_kernel + " : "";
+  char first[32] = "", name[96];
+  switch (pl.family) {
+    case Family::Batch:
+      if (pl.first_n) std::snprintf(first, sizeof(first), "rrt_first_kernel<%d, %d> + ", pl.variant, pl.first_w);
+      std::snprintf(name, sizeof(name), "%s%srrt_batch_kernel<%d, %d>", first, pass, pl.variant, pl.batch_w);
+      break;
+    case Family::PathPool:
+      std::snprintf(name, sizeof(name), "%srrt_path_kernel<%d>", pass, (pl.waves >= 2 && pl.waves <= 4) ? pl.waves : RRT_PATH_WAVES);
+      break;
+    case Family::PixelLoop:
+      std::snprintf(name, sizeof(name), "%srrt_render_kernel<%s, %s, %d, ...>", pass, tf[m.deep || m.sw || m.sky || m.disk],
+                    tf[pl.count], pl.variant == rrt::V_LEAN_POINT ? rrt::V_GENERAL : pl.variant);
+      break;
+    case Family::PerSample:
+      std::snprintf(name, sizeof(name), "%srrt_sample_kernel<%s, %d, %d, %s>", pass, tf[pl.count], pl.variant,
+                    pl.deep_sample ? (pl.waves == 2 || pl.waves == 4 ? pl.waves : 3) : pl.waves, tf[pl.deep_sample]);
+      break;
+  }
+  return name;
+}
+
+#if RRT_PROFILE
+// diagnostic build: RRT_WATCHDOG_MS=<ms> gives every batch wave and heavy block a progress record
+// in host-coherent memory and waits for the launch at most that long; on a stall it prints the
+// records of the waves that have not exited and ends the process (the hang)
+static int watchdog_arm(rrt_ctx* c, hipStream_t stream, KParams& kp, long* wd_ms) {
+  const char* wd_env = std::getenv("RRT_WATCHDOG_MS");
+  *wd_ms = wd_env ? std::atol(wd_env) : 0;
+  if (*wd_ms <= 0) return RRT_OK;
+  if (!c->h_wd) {
+    HIPCHK(c, hipHostMalloc((void**)&c->h_wd, sizeof(uint32_t) * RRT_WD_WORDS, hipHostMallocCoherent | hipHostMallocMapped));
+    HIPCHK(c, hipHostGetDevicePointer((void**)&c->d_wd, c->h_wd, 0));
+  }
+  HIPCHK(c, hipStreamSynchronize(stream));
+  std::memset(c->h_wd, 0, sizeof(uint32_t) * RRT_WD_WORDS);
+  kp.wd = c->d_wd;
+  return RRT_OK;
+}
+static void watchdog_wait(rrt_ctx* c, hipEvent_t done, long wd_ms, bool heavy) {
+  if (wd_ms <= 0) return;
+  const auto t_end = std::chrono::steady_clock::now() + std::chrono::milliseconds(wd_ms);
+  hipError_t q;
+  while ((q = hipEventQuery(done)) == hipErrorNotReady && std::chrono::steady_clock::now() < t_end)
+    std::this_thread::sleep_for(std::chrono::milliseconds(1));
+  if (q != hipErrorNotReady) return;
+  std::fprintf(stderr, "WATCHDOG: launch '%s' not done after %ld ms (grid %u, heavy list %s); live records:\n",
+               c->last_kernel.c_str(), wd_ms, c->last_grid, heavy ? "on" : "off");
+  int shown = 0, live_b = 0, live_h = 0;
+  for (uint32_t w = 0; w < RRT_WD_WORDS / 4; ++w) {
+    const volatile uint32_t* r = c->h_wd + 4 * w;
+    if (r[3] == 0 || r[3] == 0xdeadu) continue;
+    if (w < RRT_WD_HEAVY / 4) ++live_b; else ++live_h;
+    if (shown++ < 64)
+      std::fprintf(stderr, "  %s %u: it %u state 0x%x pixel %u marker 0x%x\n", w < RRT_WD_HEAVY / 4 ? "wave" : "heavy",
+                   w < RRT_WD_HEAVY / 4 ? w : w - RRT_WD_HEAVY / 4, r[0], r[1], r[2], r[3]);
+  }
+  std::fprintf(stderr, "WATCHDOG: %d batch waves and %d heavy blocks not exited\n", live_b, live_h);
+  std::fflush(stderr);
+  _exit(3);
+}
+#endif
+
+// The workspace of a plan, grown where it is too small (grow; a count of 0 grows nothing), and its pointers in kp.
+static int bind_workspace(rrt_ctx* c, const LaunchPlan& pl, uint32_t n_tiles, KParams& kp) {
+  if (c->order_cap < pl.order_n) c->h_order.clear();  // a regrown d_order holds nothing
+  int rc;
+  if ((rc = grow(c, c->d_tiles, c->tiles_cap, 2 * (size_t)n_tiles)) || (rc = grow(c, c->d_order, c->order_cap, pl.order_n)) ||
+      (rc = grow(c, c->d_first, c->first_cap, pl.first_n)) || (rc = grow(c, c->d_list, c->list_cap, pl.list_n)) ||
+      (rc = grow(c, c->d_strip_list, c->strip_list_cap, pl.strip_n)) ||
+      (rc = grow(c, c->d_heavy_list, c->heavy_list_cap, pl.heavy_cap)) ||
+      (rc = grow(c, c->d_path_stack, c->path_stack_cap, pl.path_stack_n)))
+    return rc;
+  // continuation records (rrt_sample.hip cont_push): zeroed when allocated, as no launch's tag is 0
+  if (grow(c, c->d_cont, c->cont_cap, pl.cont_cap, true)) return fail(c, RRT_E_HIP, "continuation records: allocation failed");
+  uint32_t* const word = c->d_counter;  // claim counters, then the list lengths and the continuations' control words
+  kp.tiles = c->d_tiles;
+  kp.block_counter = word;
+  if (pl.order_n) kp.tile_order = c->d_order;
+  if (pl.first_n) kp.first = c->d_first;
+  if (pl.list_n) { kp.claim_list = c->d_list; kp.claim_count = word + RRT_QUEUE_STRIDE * RRT_MAX_QUEUES; }
+  if (pl.strip_n) kp.strip_list = c->d_strip_list;
+  if (pl.heavy_cap) { kp.heavy_list = c->d_heavy_list; kp.heavy_count = word + RRT_QUEUE_STRIDE * (RRT_MAX_QUEUES + 1); }
+  if (pl.path_stack_n) kp.path_stack = c->d_path_stack;
+  if (pl.cont_cap) {
+    kp.cont = c->d_cont;
+    kp.cont_ctl = word + RRT_QUEUE_STRIDE * (RRT_MAX_QUEUES + 2);
+    kp.cont_cap = (uint32_t)c->cont_cap;
+    if (++c->cont_seq == 0) c->cont_seq = 1;
+    kp.cont_seq = c->cont_seq;
+  }
+  // run-time proof audit: counting launches that run the proofs (executed-work counts)
+  if (pl.count && kp.count_exec && c->audit_shift && c->d_audit) {
+    kp.audit = c->d_audit;
+    kp.audit_shift = c->audit_shift - 1u;
+  }
+  return RRT_OK;
+}
+
+// The only stage that touches buffers and streams: the workspace, the uploads, the kernels, the stats.
+static int enqueue(rrt_ctx* c, const rrt_render_params* p, const LaunchMode& m, const LaunchPlan& pl, KParams& kp,
+                   const uint32_t* tiles, uint32_t n_tiles, uint32_t ts, hipStream_t stream) {
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = scratch_acquire(c, stream)) return rc;
+  // whatever path leaves this function, the work already enqueued on `stream` fences the
+  // workspace for the next user on another stream
+  FenceGuard fence_guard{c, stream};
+  // once the heavy pixels' kernel is forked onto the side stream, every path out of here joins it
+  // into `stream` first (so the fence above covers its reads of d_kp / d_counter / the heavy list):
+  // 1 = launched, 2 = its completion event recorded, 3 = joined
+  struct JoinGuard {
+    rrt_ctx* c; hipStream_t s; hipStream_t fork; hipEvent_t done; int state;
+    ~JoinGuard() {
+      if (state == 1) (void)hipStreamSynchronize(fork);
+      else if (state == 2) (void)hipStreamWaitEvent(s, done, 0);
+    }
+  } join_guard{c, stream, c->side, c->ev_heavy, 0};
+  if (int rc = bind_workspace(c, pl, n_tiles, kp)) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->d_tiles, tiles, sizeof(uint32_t) * 2 * n_tiles, hipMemcpyHostToDevice, stream));
+  HIPCHK(c, hipMemsetAsync(c->d_counter, 0, kCounterBytes, stream));
+  if (pl.order_n) {
+    ClaimOrder co = claim_order(tiles, n_tiles, ts, p->frame_w, p->frame_h, pl.n_sectors, pl.ordered);
+    if (pl.family == Family::Batch)
+      for (uint32_t q = 0; q < RRT_MAX_QUEUES; ++q) kp.q_end[q] = q + 1 < pl.n_queues ? co.end[q] * ts * ts : pl.n_pixels;
+    if (co.order != c->h_order) {  // re-upload only when the tile list or its order changed
+      c->h_order.swap(co.order);
+      HIPCHK(c, hipMemcpyAsync(c->d_order, c->h_order.data(), sizeof(uint32_t) * n_tiles, hipMemcpyHostToDevice, stream));
+    }
+  }
+  c->last_grid = pl.grid;
+#if RRT_PROFILE
+  long wd_ms = 0;
+  if (int rc = watchdog_arm(c, stream, kp, &wd_ms)) return rc;
+#endif
+  HIPCHK(c, hipMemcpyAsync(c->d_kp, &kp, sizeof(KParams), hipMemcpyHostToDevice, stream));
+  const uint32_t ring = (uint32_t)(c->n_launch % rrt_ctx::kRing);
+  HIPCHK(c, hipEventRecord(c->ev0[ring], stream));
+  // the passes in front of the main kernel: sample 0 (batch), the pixel miss proof
+  if (pl.first_n) HIPCHK(c, rrt_launch_first(kp, c->d_kp, pl.variant, pl.first_w, pl.first_grid, stream));
+  if (pl.list_n) HIPCHK(c, rrt_launch_pixel_proof(c->d_kp, pl.n_pixels, pl.strip_n != 0, stream));
+  HIPCHK(c, hipEventRecord(c->ev_main[ring], stream));
+  switch (pl.family) {
+    case Family::Batch:
+      if (pl.heavy_cap) {
+        // the heavy pixels' kernel (rrt_sample.hip rrt_heavy_kernel) on the side stream (its own
+        // hardware queue), after the pass, beside the batch kernel
+        HIPCHK(c, hipEventRecord(c->ev_go, stream));
+        HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_go, 0));
+        join_guard.state = 1;
+        HIPCHK(c, rrt_launch_heavy(c->d_kp, pl.variant, pl.heavy_w, pl.heavy_nw, pl.heavy_grid, RRT_HEAVY_LIST, c->side));
+        HIPCHK(c, hipEventRecord(c->ev_heavy, c->side));
+        join_guard.state = 2;
+      }
+      HIPCHK(c, rrt_launch_batch(kp, c->d_kp, pl.variant, pl.batch_w, pl.bgrid, stream));
+      if (pl.heavy_cap) {
+        HIPCHK(c, hipStreamWaitEvent(stream, c->ev_heavy, 0));
+        join_guard.state = 3;
+        // continuations no block took (every waiter stopped first): rendered behind the kernels
+        if (pl.cont_cap) HIPCHK(c, rrt_launch_heavy(c->d_kp, pl.variant, pl.heavy_w, pl.heavy_nw, 16u, RRT_HEAVY_DRAIN, stream));
+      }
+      break;
+    case Family::PathPool: HIPCHK(c, rrt_launch_path(c->d_kp, pl.waves, pl.grid, stream)); break;
+    case Family::PixelLoop: HIPCHK(c, rrt_launch_render(kp, c->d_kp, pl.deep, pl.count, pl.variant, pl.waves, pl.grid, stream)); break;
+    case Family::PerSample: HIPCHK(c, rrt_launch_sample(kp, c->d_kp, pl.count, pl.variant, pl.waves, pl.grid, stream)); break;
+  }
+  c->last_kernel = kernel_name(pl, m);
+  c->last_heavy = pl.heavy_cap;
+  c->last_cont = pl.cont_cap ? kp.cont_cap : 0u;
+  HIPCHK(c, hipEventRecord(c->ev1[ring], stream));
+#if RRT_PROFILE
+  watchdog_wait(c, c->ev1[ring], wd_ms, pl.heavy_cap != 0);
+#endif
+  c->timed = true;
+  ++c->n_launch;
+  return RRT_OK;
+}
+
+static int launch(rrt_ctx* c, const rrt_render_params* p, const uint32_t* tiles, uint32_t n_tiles, uint32_t ts,
+                  uint32_t cx0, uint32_t cy0, uint32_t cx1, uint32_t cy1, float* d_rgb, int32_t* d_cnt,
+                  uint32_t* d_draws, uint32_t* d_ctr, hipStream_t stream) {
+  const LaunchMode m = launch_mode(c, p, d_ctr != nullptr);
+  if (int rc = check_launch(c, p, m, n_tiles, ts)) return rc == kLaunchEmpty ? RRT_OK : rc;
+  KParams kp{};
+  fill_scene_params(c, p->flags, kp);
+  const bool proofs_valid = fill_proof_params(c, p->flags, kp);
+  // the launch's own constants: the render settings, the frame, the tile list's shape and the outputs
   kp.ns_aa = p->ns_aa; kp.max_ray_depth = p->max_ray_depth; kp.ns_area_light = p->ns_area_light;
   kp.samples_per_batch = p->samples_per_batch; kp.max_tolerance = p->max_tolerance;
   kp.direct_hemisphere = p->direct_hemisphere; kp.seed = p->seed;
@@ -1651,492 +2177,19 @@ static int launch(rrt_ctx* c, const rrt_render_params* p, const uint32_t* tiles,
   kp.count_exec = (p->flags & RRT_RENDER_COUNT_EXECUTED) ? 1u : 0u;
   kp.frame_w = (double)p->frame_w; kp.frame_h = (double)p->frame_h;
   kp.frame_wi = p->frame_w; kp.frame_hi = p->frame_h;
-  kp.tiles = c->d_tiles; kp.n_tiles = n_tiles; kp.tile_size = ts;
+  kp.n_tiles = n_tiles; kp.tile_size = ts;
   kp.blocks_per_tile_side = ts / 8;
   kp.n_blocks = n_tiles * (ts / 8) * (ts / 8);
-  kp.block_counter = c->d_counter;
   kp.clip_x0 = cx0; kp.clip_y0 = cy0; kp.clip_x1 = cx1; kp.clip_y1 = cy1;
   kp.rgb = d_rgb; kp.count = d_cnt; kp.draws = d_draws; kp.counters = d_ctr;
-  // Kernel choice (depth <= 1): the per-sample kernel (rrt_sample.hip) by default;
-  // RRT_RENDER_PIXEL_LOOP selects the general per-pixel-loop kernel (rrt_kernel.hip, also used
-  // for depth >= 2).  LEAN
-  // builds when the scene allows them; variant = register budget in waves per SIMD.
-  const int deep = p->max_ray_depth >= 2 ? 1 : 0;
-  const int count = (p->flags & RRT_RENDER_COUNTERS) && d_ctr ? 1 : 0;
-  // kernel variant (rrt_device.h): the Kerr builds for a Kerr spacetime; else LEAN builds when
-  // the scene allows (no environment map, importance-sampled direct light), else general
-  const bool kerr = c->hole.kind == RRT_METRIC_KERR;
-  // the reference's compile-time switches (RRT_RENDER_THIN_LENS .. RRT_RENDER_ILLUM_MASK): the
-  // general per-pixel-loop build V_SW (rrt_kernel.hip), every ray marched exactly
-  kp.sw = (p->flags >> 22) & 63u;
+  kp.sw = (p->flags >> 22) & 63u;  // the build V_SW (rrt_kernel.hip)
   kp.lens_r = c->lens_r; kp.focal = c->focal;
-  const bool sw = kp.sw != 0;
-  if (sw && kerr) return fail(c, RRT_E_INVALID, "the reference's switches (THIN_LENS, ADAPTIVE, ILLUM, ENV_HEMI, "
-                                                "MICROFACET_HEMI) are built for the Schwarzschild stepper only");
-  if (sw && ((kp.sw >> 4) ^ 2u) == 3u && p->max_ray_depth == 0)
-    return fail(c, RRT_E_INVALID, "ILLUM 3 with max_ray_depth 0: the reference's recursion depth is unbounded there "
-                                  "(Ray::depth is size_t and wraps below 0; only Russian roulette ends it), beyond "
-                                  "RRT_MAX_DEPTH");
-  if (sw) { kp.miss.on = 0u; kp.occ.on = 0u; }
-  // the lensed sky (RRT_SPACETIME_LENSED_SKY): the general per-pixel-loop builds V_SKY /
-  // V_KERR_SKY (rrt_kernel.hip), every query the exit-mode march, no proof
-  const bool sky = c->lensed_sky;
-  if (sky && (sw || (p->flags & (RRT_RENDER_WAVEFRONT | RRT_RENDER_DEEP_SAMPLE | RRT_RENDER_COUNTERS))))
-    return fail(c, RRT_E_INVALID, "the lensed sky (RRT_SPACETIME_LENSED_SKY) renders in the per-pixel-loop kernel only: "
-                                  "not with RRT_RENDER_WAVEFRONT, RRT_RENDER_DEEP_SAMPLE, RRT_RENDER_COUNTERS or the "
-                                  "reference's switch flags");
-  if (sky) { kp.miss.on = 0u; kp.occ.on = 0u; kp.kproof.on = 0u; }
-  // the accretion disk (rrt_set_disk): the general per-pixel-loop build V_KERR_DISK
-  // (rrt_kernel.hip), every query the exit-mode march with the disk test, no proof; the lensed sky's rule
-  const bool disk = c->has_disk;
-  if (disk && (sw || (p->flags & (RRT_RENDER_WAVEFRONT | RRT_RENDER_DEEP_SAMPLE | RRT_RENDER_COUNTERS))))
-    return fail(c, RRT_E_INVALID, "the accretion disk (rrt_set_disk) renders in the per-pixel-loop kernel only: not with "
-                                  "RRT_RENDER_WAVEFRONT, RRT_RENDER_DEEP_SAMPLE, RRT_RENDER_COUNTERS or the reference's "
-                                  "switch flags");
-  if (int rc = fill_disk_params(c, kp)) return rc;
-  if (disk) { kp.miss.on = 0u; kp.occ.on = 0u; kp.kproof.on = 0u; }
-  // bounce paths (depth >= 2): the per-pixel-loop kernel by default; RRT_RENDER_DEEP_SAMPLE selects
-  // the per-sample refill kernel (rrt_sample.hip, one lane per pixel, a lane whose pixel is done
-  // takes the next at the next sample boundary) -- m3 A/B, profiles/r03_ab_deep.jsonl: 177 ms
-  // pixel loop vs 236 ms refill at 3 waves/SIMD, identical outputs
-  const bool deep_sample = deep && !count && !kerr && !sw && (p->flags & RRT_RENDER_DEEP_SAMPLE) &&
-                           !(p->flags & RRT_RENDER_PIXEL_LOOP);
-  // RRT_RENDER_WAVEFRONT: the bounce paths (depth >= 2, Schwarzschild) in the path pool kernel
-  // (rrt_path.hip: one ray per lane per round, the paths' integrator state between rays in LDS),
-  // an A/B variant: m3 269 ms at 3 waves/SIMD vs 172 ms for the per-pixel loop.
-  // Its light-sample cursor holds 11 bits: n_lights x ns_area_light < 2048.
-  const bool path_pool = (p->flags & RRT_RENDER_WAVEFRONT) != 0;
-  // its path records pack the pixel as x | y << 16
-  if (path_pool && (p->frame_w > 65535u || p->frame_h > 65535u))
-    return fail(c, RRT_E_INVALID, "RRT_RENDER_WAVEFRONT (the path pool kernel) renders frames of at most 65535 pixels a side");
-  if (path_pool && !(deep && !count && !kerr && !sw && p->ns_aa >= 1 &&
-                     (uint64_t)all_lights(c).size() * std::max<uint32_t>(1u, p->ns_area_light) < 2048u))
-    return fail(c, RRT_E_INVALID, "RRT_RENDER_WAVEFRONT (the path pool kernel) renders max_ray_depth >= 2 "
-                                  "Schwarzschild frames without counters or switches, n_lights x ns_area_light < 2048");
-  const bool pixel_loop = !path_pool && ((deep && !deep_sample) || (p->flags & RRT_RENDER_PIXEL_LOOP) || sw || sky || disk);
-  const bool disk_pt = disk && kp.disk.blackbody && kp.disk.profile == RRT_DISK_PROFILE_PAGE_THORNE;
-  const int lean = disk_pt ? (kp.disk.light ? 12 /* V_KERR_DISK_PT_LIGHT */ : 11 /* V_KERR_DISK_PT */)
-                 : disk ? (kp.disk.light ? (kp.disk.blackbody ? 10 /* V_KERR_DISK_BB_LIGHT */ : 9 /* V_KERR_DISK_LIGHT */)
-                                         : (kp.disk.blackbody ? 8 /* V_KERR_DISK_BB */ : 7 /* V_KERR_DISK */))
-                 : sky ? (kerr ? 6 /* V_KERR_SKY */ : 5 /* V_SKY */)
-                 : kerr ? 3 /* V_KERR */
-                 : sw ? 4 /* V_SW */
-                 : (!deep && !count && !c->env_w && !p->direct_hemisphere) ? c->lean : 0;
-  const uint32_t wv = p->variant & 0xffu;
-  // bounce builds: 3 waves/SIMD (m3 A/B, profiles/r03_ab_deep.jsonl: 363 / 263 / 180 / 180 ms at 1 / 2 / 3 / 4)
-  const int waves = (wv >= 1 && wv <= 6) ? (int)wv : path_pool ? RRT_PATH_WAVES : deep ? 3 : (pixel_loop ? 2 : 3);
-  // persistent grid, 4 waves per block, up to 8 blocks per CU (the 32-wave limit): as many
-  // blocks as the kernel's registers allow become resident; any others start when a resident
-  // block exits and find the atomic work counter exhausted
-  // Sample-parallel kernel (rrt_sample.hip rrt_batch_kernel) whenever a pixel takes more than
-  // one sample: it needs each camera sample's RNG draw count to depend only on whether its query
-  // hit, which holds at depth <= 1 (jitter + the direct-lighting samplers).
-  const bool batch = !deep && !count && !pixel_loop && std::min(p->ns_aa, p->samples_per_batch) >= 5 &&
-                     !(p->flags & RRT_RENDER_PER_PIXEL);
-  // Continuations (rrt_sample.hip cont_push): the records, their control words and
-  // the heavy blocks' waiting policy.  A/B in the environment: RRT_AB_CONT_MIN=samples left;
-  // RRT_AB_CONT_ROOM=batch blocks of room; RRT_AB_CONT_WAITERS=heavy blocks that wait.  false: HIP error
-  auto setup_cont = [&](bool part) -> bool {
-    const uint32_t ccap = std::min<uint32_t>(kp.n_pixels, std::max<uint32_t>(4096u, kp.n_pixels / 256u));
-    if (c->cont_cap < ccap) {
-      hipFree(c->d_cont); c->d_cont = nullptr; c->cont_cap = 0;
-      if (hipMalloc(&c->d_cont, sizeof(ContRec) * ccap) != hipSuccess ||
-          hipMemset(c->d_cont, 0, sizeof(ContRec) * ccap) != hipSuccess) {
-        fail(c, RRT_E_HIP, "continuation records: allocation failed");
-        return false;
-      }
-      c->cont_cap = ccap;
-    }
-    kp.cont = c->d_cont;
-    kp.cont_ctl = c->d_counter + RRT_QUEUE_STRIDE * (RRT_MAX_QUEUES + 2);
-    kp.cont_cap = (uint32_t)c->cont_cap;
-    const char* cm = std::getenv("RRT_AB_CONT_MIN");
-    kp.cont_min_left = cm ? (uint32_t)std::strtoul(cm, nullptr, 10) : 2u * p->samples_per_batch;
-    if (++c->cont_seq == 0) c->cont_seq = 1;
-    kp.cont_seq = c->cont_seq;
-    // room for 32 heavy blocks from the launch's start (a rank's first pixels are its centre's,
-    // the costliest: their first checks come early)
-    const char* cr = std::getenv("RRT_AB_CONT_ROOM");
-    kp.cont_room = cr ? (uint32_t)std::strtoul(cr, nullptr, 10) : (part ? 32u : 0u);
-    kp.cont_ticks = 5000000u;  // 50 ms of wall clock (100 MHz)
-    const char* cw = std::getenv("RRT_AB_CONT_WAITERS");
-    kp.cont_waiters = cw ? (uint32_t)std::strtoul(cw, nullptr, 10) : ~0u;
-    return true;
-  };
-  if (batch) {
-    kp.draws_miss = 2;
-    uint32_t dh = 2;
-    if (p->max_ray_depth >= 1) {
-      if (p->direct_hemisphere) {
-        dh += 2u * (uint32_t)all_lights(c).size() * p->ns_area_light;
-      } else {
-        for (const DLight& l : all_lights(c)) {
-          const uint32_t num = l.is_delta ? 1u : p->ns_area_light;
-          // area, hemisphere and environment samplers draw 2 each; point / directional none
-          const bool sampled = l.type == RRT_LIGHT_AREA || l.type == RRT_LIGHT_HEMISPHERE || l.type == 5u;
-          dh += sampled ? 2u * num : 0u;
-        }
-      }
-    }
-    kp.draws_hit = dh;
-    uint32_t gsz = 8;  // groups of 8..32 lanes (GroupLds holds 32 groups per block)
-    const uint32_t want_g = std::min<uint32_t>(std::min<uint32_t>(p->ns_aa, p->samples_per_batch), 32u);
-    while (gsz < want_g) gsz <<= 1;
-    kp.group = gsz;
-    kp.n_pixels = n_tiles * ts * ts;
-    // Claim order: tiles nearest the frame centre first (where the geometry and the black hole's
-    // ring usually are), so the launch ends on cheap border tiles rather than on a costly
-    // region; consecutive claims stay spatially adjacent (coherent waves, warm caches).
-    // One queue per XCD (workgroups are dealt to the 8 XCDs round-robin, so block b starts on
-    // queue b % 8): queue q holds the tiles of the q-th 45-degree sector about the frame centre,
-    // centre-first.  Each XCD's L2 then serves a coherent wedge of the frame (a narrower slice
-    // of the BVH), every wedge gets its share of the costly centre, and a block whose queue is
-    // empty moves on to the next queue, so the load still balances at pixel granularity.
-    std::vector<uint32_t> order(n_tiles);
-    for (uint32_t k = 0; k < n_tiles; ++k) order[k] = k;
-    const bool ordered = p->flags & RRT_RENDER_ORDERED;
-    // A/B (profiles/r01_queues_ab.md): per-XCD queues cost the LEAN cfg3 build 6% and save the
-    // Kerr cfg5 build 2%, so they are the default for the general / Kerr builds only
-    const bool xcd_q = (p->flags & RRT_RENDER_XCD_QUEUES) || ((lean == 0 || lean == 3) && !(p->flags & RRT_RENDER_ONE_QUEUE) &&
-                                                             !(p->flags & RRT_RENDER_STRIPED_QUEUES));
-    // Striped queues (the LEAN default): the centre-first order dealt round-robin over one
-    // counter per XCD, so the claim atomics spread over 8 addresses while the order stays global
-    const bool striped = !ordered && !(p->flags & RRT_RENDER_ONE_QUEUE) && !(p->flags & RRT_RENDER_XCD_QUEUES) &&
-                         ((p->flags & RRT_RENDER_STRIPED_QUEUES) || lean == 1 || lean == 2);
-    const uint32_t nq = (ordered || !(xcd_q || striped)) ? 1u : RRT_MAX_QUEUES;
-    kp.q_stripe = striped ? 1u : 0u;
-    std::vector<uint32_t> sector(n_tiles, 0);
-    if (!ordered) {
-      const double cx = 0.5 * p->frame_w, cy = 0.5 * p->frame_h;
-      std::vector<double> key(n_tiles);
-      for (uint32_t k = 0; k < n_tiles; ++k) {
-        const double dx = tiles[2 * k] + 0.5 * ts - cx, dy = tiles[2 * k + 1] + 0.5 * ts - cy;
-        key[k] = dx * dx + dy * dy;
-        if (nq > 1 && !striped) {
-          const double a = std::atan2(dy, dx) + kPI;  // [0, 2 pi]
-          sector[k] = std::min<uint32_t>((uint32_t)(a * (nq / (2 * kPI))), nq - 1);
-        }
-      }
-      std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-        return sector[a] != sector[b] ? sector[a] < sector[b] : key[a] < key[b];
-      });
-    }
-    kp.n_queues = nq;
-    for (uint32_t q = 0, k = 0; q < RRT_MAX_QUEUES; ++q) {
-      while (k < n_tiles && sector[order[k]] == q) ++k;
-      kp.q_end[q] = q < nq ? k * ts * ts : kp.n_pixels;
-    }
-    kp.q_end[nq - 1] = kp.n_pixels;
-    if (c->order_cap < n_tiles) {
-      hipFree(c->d_order); c->d_order = nullptr;
-      HIPCHK(c, hipMalloc(&c->d_order, sizeof(uint32_t) * n_tiles));
-      c->order_cap = n_tiles;
-      c->h_order.clear();
-    }
-    if (order != c->h_order) {  // re-upload only when the tile list or its order changed
-      c->h_order = order;
-      HIPCHK(c, hipMemcpyAsync(c->d_order, c->h_order.data(), sizeof(uint32_t) * n_tiles, hipMemcpyHostToDevice,
-                               stream));
-    }
-    kp.tile_order = c->d_order;
-    kp.first = nullptr;
-    kp.claim_list = nullptr; kp.claim_count = nullptr;
-    // sample-0 pre-pass: off by default (with the slot speculation a wrong first hypothesis
-    // costs one round, less than the extra pass; tools/ab_kernels.py cfg3 46.4 vs 47.8 ms)
-    if ((p->flags & RRT_RENDER_PREPASS) && !(p->flags & RRT_RENDER_NO_FIRST)) {
-      if (c->first_cap < kp.n_pixels) {
-        hipFree(c->d_first); c->d_first = nullptr;
-        HIPCHK(c, hipMalloc(&c->d_first, sizeof(KParams::FirstSample) * kp.n_pixels));
-        c->first_cap = kp.n_pixels;
-      }
-      kp.first = c->d_first;
-    }
-    // pixel miss proof pass (rrt_pixel_proof_kernel): the area/point-light builds, whose misses
-    // are black, with a claim order it can compact (striped or one queue); list entries keep bit
-    // 31 for the first-hypothesis hint
-    // The pass writes a proven pixel's result as the first adaptive check's stop on all-zero
-    // samples, which holds only when 1.96 * 0 <= max_tolerance * 0 (a finite tolerance; with an
-    // infinite or NaN one the reference runs all ns_aa samples, part1_code.cpp:147-158)
-    const bool zero_stops = 0.0 <= (double)p->max_tolerance * 0.0 && p->samples_per_batch >= 2;
-    if ((lean == 1 || lean == 2) && proofs_valid && zero_stops && !c->env_w && !kp.first && (striped || nq == 1) &&
-        kp.n_pixels < 0x80000000u && !(p->flags & RRT_RENDER_NO_PIXEL_PROOF)) {
-      if (c->list_cap < kp.n_pixels) {
-        hipFree(c->d_list); c->d_list = nullptr;
-        HIPCHK(c, hipMalloc(&c->d_list, sizeof(uint32_t) * kp.n_pixels));
-        c->list_cap = kp.n_pixels;
-      }
-      kp.claim_list = c->d_list;
-      kp.claim_count = c->d_counter + RRT_QUEUE_STRIDE * RRT_MAX_QUEUES;
-      // hit-first claim order (rrt_pixel_proof_kernel); variant bit 22: the pass's order (A/B)
-      kp.claim_back = ((p->variant >> 22) & 1u) ? 0u : 1u;
-      // Heavy pixels (rrt_device.h pixel_heavy): the pass lists them apart and rrt_heavy_kernel
-      // renders them slot-parallel, a block of waves per pixel (rrt_sample.hip
-      // heavy_pixel_block); needs a hit to take a whole number of slots (Dh = k Dm)
-      // Where the heavy pixels' latency bounds the launch: launches covering at most 60% of the
-      // frame (one rank's tiles of a multi-GPU frame, the regions of the host path; cfg3 split 8
-      // ways, slowest rank 8.1 -> 4.4 ms), and pixels of 4 or more adaptive steps, whose chains of
-      // rounds outlast the frame (cfg4, 256 spp: 16.5 -> 15.0 ms).  A whole cfg3 frame (2 steps a
-      // pixel) is bound by its throughput, and the heavy kernel's room in the batch grid costs more
-      // than it saves (18.3 -> 19.0 ms).
-      const uint64_t frame_px = (uint64_t)p->frame_w * p->frame_h;
-      const bool share_ok = (p->flags & RRT_RENDER_HEAVY) || (uint64_t)kp.n_pixels * 5u <= frame_px * 3u ||
-                            p->ns_aa >= 4u * p->samples_per_batch;
-      if (!(p->flags & RRT_RENDER_NO_HEAVY) && share_ok && c->hole.r > 0.0 && kp.draws_hit % kp.draws_miss == 0) {
-        // at most 1/256 of the pixels (4096 at least): a frame mostly near the hole stays with
-        // the batch kernel, whose rounds cost less than 64 slots a step for unmixed pixels
-        const uint32_t cap = std::min<uint32_t>(kp.n_pixels, std::max<uint32_t>(4096u, kp.n_pixels / 256u));
-        if (c->heavy_list_cap < cap) {
-          hipFree(c->d_heavy_list); c->d_heavy_list = nullptr;
-          HIPCHK(c, hipMalloc(&c->d_heavy_list, sizeof(uint32_t) * cap));
-          c->heavy_list_cap = cap;
-        }
-        kp.heavy_list = c->d_heavy_list;
-        kp.heavy_count = c->d_counter + RRT_QUEUE_STRIDE * (RRT_MAX_QUEUES + 1);
-        kp.heavy_cap = cap;
-
-        // A/B (variant bits 16..19): 1: capture-boundary pixels only, 2 .. 6: near 1.1 / 1.5 / 2.0 / 3.0 / 5.0
-        const uint32_t nv = (p->variant >> 16) & 0xfu;
-        const double near = nv == 1 ? 0.0 : nv == 2 ? 1.1 : nv == 3 ? 1.5 : nv == 4 ? 2.0 : nv == 5 ? 3.0 : nv == 6 ? 5.0 : RRT_HEAVY_NEAR;
-        kp.heavy_r2 = (near * c->hole.r) * (near * c->hole.r);
-        // Continuations (rrt_sample.hip cont_push): in launches of at most 60% of the
-        // frame (a rank's share), pixels of three or more adaptive steps go to waiting heavy blocks
-        // after a check with two or more steps to go (cfg4, 256 spp: the 8-way split's ranks ended
-        // on a few 8-step pixels, one step a round on the group path; profiles/r06_cont_w8_cfg4.txt).
-        // A whole frame keeps them on the group path (its waiting heavy blocks cost ~2%).
-        // A/B in the environment: RRT_AB_CONT=0 off / 1 on for any launch; RRT_AB_CONT_MIN=samples
-        // left; RRT_AB_CONT_ROOM=batch blocks of room; RRT_AB_CONT_WAITERS=heavy blocks that wait
-        const char* ce = std::getenv("RRT_AB_CONT");
-        const bool part = (uint64_t)kp.n_pixels * 5u <= frame_px * 3u;
-        const bool cont_on = p->ns_aa >= 3u * p->samples_per_batch && (ce ? ce[0] == '1' : part);
-        if (cont_on && !setup_cont(part)) return RRT_E_HIP;
-      }
-    }
-  }
-  // The bounce (depth >= 2) per-pixel-loop kernel behind the pixel miss proof pass: a proven
-  // pixel's samples all miss at any depth (est_radiance returns the black miss, 2 draws each), so
-  // the pass writes it and the kernel claims only the listed pixels, 64 per wave, in a
-  // centre-first order
-  // The path pool kernel claims from the same centre-first order, listed or not.
-  const bool deep_list = deep && !count && !sw && proofs_valid && !c->env_w && !kerr && kp.miss.on &&
-                         0.0 <= (double)p->max_tolerance * 0.0 && p->samples_per_batch >= 2 &&
-                         !(p->flags & RRT_RENDER_NO_PIXEL_PROOF);
-  if (deep_list || path_pool) {
-    kp.draws_miss = 2;
-    kp.n_pixels = n_tiles * ts * ts;
-    std::vector<uint32_t> order(n_tiles);
-    for (uint32_t k = 0; k < n_tiles; ++k) order[k] = k;
-    if (!(p->flags & RRT_RENDER_ORDERED)) {
-      const double cx = 0.5 * p->frame_w, cy = 0.5 * p->frame_h;
-      std::vector<double> key(n_tiles);
-      for (uint32_t k = 0; k < n_tiles; ++k) {
-        const double dx = tiles[2 * k] + 0.5 * ts - cx, dy = tiles[2 * k + 1] + 0.5 * ts - cy;
-        key[k] = dx * dx + dy * dy;
-      }
-      std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
-    }
-    if (c->order_cap < n_tiles) {
-      hipFree(c->d_order); c->d_order = nullptr;
-      HIPCHK(c, hipMalloc(&c->d_order, sizeof(uint32_t) * n_tiles));
-      c->order_cap = n_tiles;
-      c->h_order.clear();
-    }
-    if (order != c->h_order) {
-      c->h_order = order;
-      HIPCHK(c, hipMemcpyAsync(c->d_order, c->h_order.data(), sizeof(uint32_t) * n_tiles, hipMemcpyHostToDevice, stream));
-    }
-    kp.tile_order = c->d_order;
-    if (deep_list) {
-      if (c->list_cap < kp.n_pixels) {
-        hipFree(c->d_list); c->d_list = nullptr;
-        HIPCHK(c, hipMalloc(&c->d_list, sizeof(uint32_t) * kp.n_pixels));
-        c->list_cap = kp.n_pixels;
-      }
-      kp.claim_list = c->d_list;
-      kp.claim_count = c->d_counter + RRT_QUEUE_STRIDE * RRT_MAX_QUEUES;
-    }
-  }
-  // the pass's strip level: tiles whose rows split into strips of 64 claim indices (ts | 64 or 64 | ts)
-  if (kp.claim_list && kp.n_pixels >= 64u) {
-    const size_t ns = kp.n_pixels / 64u;
-    if (c->strip_list_cap < ns) {
-      hipFree(c->d_strip_list); c->d_strip_list = nullptr;
-      HIPCHK(c, hipMalloc(&c->d_strip_list, sizeof(uint32_t) * ns));
-      c->strip_list_cap = ns;
-    }
-    kp.strip_list = c->d_strip_list;
-  }
-  // run-time proof audit: counting launches that run the proofs (executed-work counts)
-  if (count && kp.count_exec && c->audit_shift && c->d_audit) {
-    kp.audit = c->d_audit;
-    kp.audit_shift = c->audit_shift - 1u;
-  }
-  uint32_t want = batch ? (uint32_t)(((uint64_t)kp.n_pixels * kp.group + 255) / 256) : (kp.n_blocks + 3) / 4;
-  uint32_t grid = std::min<uint32_t>(want, (uint32_t)c->n_cu * 8u);
-  if (path_pool) {  // 256 paths a block, the resident blocks only (each path holds a stack slot)
-    const uint32_t pw = (waves >= 2 && waves <= 4) ? (uint32_t)waves : (uint32_t)RRT_PATH_WAVES;
-    grid = std::min<uint32_t>((kp.n_pixels + 255u) / 256u, (uint32_t)c->n_cu * pw);
-    if (grid == 0) grid = 1;
-    // levels 0 .. max_ray_depth - 1 of the recursion, then each path's pixel record
-    const size_t bytes = sizeof(float) * RRT_PATH_FIELDS * ((size_t)p->max_ray_depth + 1u) * grid * 256u;
-    if (c->path_stack_cap < bytes) {
-      hipFree(c->d_path_stack); c->d_path_stack = nullptr; c->path_stack_cap = 0;
-      HIPCHK(c, hipMalloc(&c->d_path_stack, bytes));
-      c->path_stack_cap = bytes;
-    }
-    kp.path_stack = c->d_path_stack;
-  }
-  if (grid == 0) grid = 1;
-  c->last_grid = grid;
-#if RRT_PROFILE
-  // diagnostic build: RRT_WATCHDOG_MS=<ms> gives every batch wave and heavy block a progress record
-  // in host-coherent memory and waits for the launch at most that long; on a stall it prints the
-  // records of the waves that have not exited and ends the process (the hang)
-  const char* wd_env = std::getenv("RRT_WATCHDOG_MS");
-  const long wd_ms = wd_env ? std::atol(wd_env) : 0;
-  if (wd_ms > 0) {
-    if (!c->h_wd) {
-      HIPCHK(c, hipHostMalloc((void**)&c->h_wd, sizeof(uint32_t) * RRT_WD_WORDS, hipHostMallocCoherent | hipHostMallocMapped));
-      HIPCHK(c, hipHostGetDevicePointer((void**)&c->d_wd, c->h_wd, 0));
-    }
-    HIPCHK(c, hipStreamSynchronize(stream));
-    std::memset(c->h_wd, 0, sizeof(uint32_t) * RRT_WD_WORDS);
-    kp.wd = c->d_wd;
-  }
-#endif
-  // the heavy pixels' kernel (batch launches with a heavy list): its waves per pixel and grid, and
-  // whether the batch kernel sizes its room for it on the device (variant bits 22 / 23: A/B)
-  const uint32_t hgv = (p->variant >> 28) & 0xfu, nwv = (p->variant >> 20) & 3u;
-  // waves per heavy pixel: 2 (a 64-sample pixel's two steps in one round), 4 with continuations
-  // (256 slots a round: the rest of a 256-sample pixel); A/B: variant bits 20..21 = 1 / 2 / 3:
-  // 1 (2 for the point-light build) / 4 / 2
-  const int heavy_nw = nwv == 0 ? (kp.cont ? 4 : 2) : nwv == 1 ? (lean == 2 ? 2 : 1) : nwv == 2 ? 4 : 2;
-  // heavy waves: hgv x the CU count (default 2), in blocks of heavy_nw waves
-  const uint32_t heavy_waves = std::min<uint32_t>((uint32_t)c->n_cu * (hgv ? hgv : 2u), (uint32_t)c->n_cu * 4u);
-  const uint32_t heavy_grid = std::max<uint32_t>(1u, heavy_waves / (uint32_t)heavy_nw);
-  const bool no_room = (p->variant >> 23) & 1u;      // A/B: leave the batch grid as it is
-  // A/B: round 3's fixed room, of (variant bits 12..15) - 1 blocks per CU beyond the heavy waves
-  const bool static_room = ((p->variant >> 12) & 0xfu) != 0u;
-  if (batch && kp.heavy_list && !no_room && !static_room) {
-    kp.heavy_grid = heavy_grid;
-    kp.heavy_nw = (uint32_t)heavy_nw;
-  }
-  // the batch kernel's waves/SIMD and grid (known before the upload: the heavy kernel's
-  // continuation wait ends when all kp.batch_waves batch waves have exited)
-  // waves/SIMD: the area-light build at 4 (cfg3 15.71 -> 15.33 ms, cfg2 10.33 -> 10.01 ms against
-  // 5, since the search tree took the local oversized leaves), the point-light build at 5 (cfg4
-  // 14.15 ms against 14.65 at 4) -- profiles/r03_heavy_ab.md
-  const int bw = (wv >= 2 && wv <= 5) ? (int)wv : 4;
-  // general / Kerr builds: 3 waves/SIMD by default (cfg5: 4.56 s at 2 waves, 3.37 s at 3)
-  const int gw = (wv >= 2 && wv <= 5) ? (int)wv : 3;
-  const int batch_w = lean == 1 ? bw : lean == 2 ? (wv >= 3 && wv <= 5 ? (int)wv : 5) : gw;
-  uint32_t bgrid = grid;
-  if (batch && kp.heavy_list) {
-    // the batch grid leaves room for the heavy kernel's blocks (one per CU at most, <= 128 VGPRs
-    // and 25 KB of LDS next to four batch blocks), whichever kernel the hardware dispatches first
-    const uint32_t resident = (uint32_t)c->n_cu * (uint32_t)batch_w;  // blocks of 4 waves
-    const uint32_t spare = (static_room ? ((p->variant >> 12) & 0xfu) - 1u : 0u) * (uint32_t)c->n_cu +
-                           (heavy_waves + 3u) / 4u;  // room, in batch blocks
-    if (static_room) {
-      if (!no_room && bgrid + spare > resident) bgrid = resident > spare ? resident - spare : 1u;
-    } else if (!no_room) {
-      // room sized on the device to the heavy pixels the pass found (rrt_batch_kernel prologue,
-      // kp.heavy_grid / heavy_nw): the grid is exactly the resident blocks, so a block that
-      // leaves frees a slot no pending batch block can take
-      bgrid = std::min(bgrid, resident);
-    }
-  }
-  kp.batch_waves = bgrid * 4u;
-
-  // tail priority threshold (A/B: RRT_AB_PRIO_TICKS in the environment)
-  kp.prio_ticks = 50000u;
-  if (const char* pt = std::getenv("RRT_AB_PRIO_TICKS")) kp.prio_ticks = (uint32_t)std::strtoul(pt, nullptr, 10);
-  HIPCHK(c, hipMemcpyAsync(c->d_kp, &kp, sizeof(KParams), hipMemcpyHostToDevice, stream));
-  const uint32_t ring = (uint32_t)(c->n_launch % rrt_ctx::kRing);
-  HIPCHK(c, hipEventRecord(c->ev0[ring], stream));
-  const char* tf[2] = {"false", "true"};
-  char name[96];
-  if (batch) {
-    const int w = batch_w;
-    char first[32] = "";
-    const uint32_t fwv = (p->variant >> 8) & 0xfu;  // pre-pass waves/SIMD (A/B), default 3
-    const int fw = (lean == 1 && (fwv == 4 || fwv == 5)) ? (int)fwv : 3;
-    if (kp.first) std::snprintf(first, sizeof(first), "rrt_first_kernel<%d, %d> + ", lean, fw);
-    if (kp.claim_list) std::snprintf(first, sizeof(first), "rrt_pixel_proof_kernel + ");
-    std::snprintf(name, sizeof(name), "%srrt_batch_kernel<%d, %d>", first, lean, w);
-    if (kp.first)
-      HIPCHK(c, rrt_launch_first(kp, c->d_kp, lean, fw, std::min<uint32_t>((kp.n_pixels + 255) / 256, (uint32_t)c->n_cu * 8u),
-                                 stream));
-    if (kp.claim_list) HIPCHK(c, rrt_launch_pixel_proof(c->d_kp, kp.n_pixels, kp.strip_list != nullptr, stream));
-    HIPCHK(c, hipEventRecord(c->ev_main[ring], stream));
-    const uint32_t hwv = (p->variant >> 24) & 0xfu;
-    const int hw = hwv == 5 ? 5 : 4;  // the heavy kernel's waves/SIMD budget
-    if (kp.heavy_list) {
-      // the heavy pixels' kernel (rrt_sample.hip rrt_heavy_kernel) on the side stream (its own
-      // hardware queue), after the pass, beside the batch kernel
-      HIPCHK(c, hipEventRecord(c->ev_go, stream));
-      HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_go, 0));
-      join_guard.state = 1;
-      HIPCHK(c, rrt_launch_heavy(c->d_kp, lean, hw, heavy_nw, heavy_grid, RRT_HEAVY_LIST, c->side));
-      HIPCHK(c, hipEventRecord(c->ev_heavy, c->side));
-      join_guard.state = 2;
-    }
-    HIPCHK(c, rrt_launch_batch(kp, c->d_kp, lean, w, bgrid, stream));
-    if (kp.heavy_list) {
-      HIPCHK(c, hipStreamWaitEvent(stream, c->ev_heavy, 0));
-      join_guard.state = 3;
-      // continuations no block took (every waiter stopped first): rendered behind the kernels
-      if (kp.cont) HIPCHK(c, rrt_launch_heavy(c->d_kp, lean, hw, heavy_nw, 16u, RRT_HEAVY_DRAIN, stream));
-    }
-  } else if (path_pool) {
-    std::snprintf(name, sizeof(name), "%srrt_path_kernel<%d>", deep_list ? "rrt_pixel_proof_kernel + " : "",
-                  (waves >= 2 && waves <= 4) ? waves : RRT_PATH_WAVES);
-    if (deep_list) HIPCHK(c, rrt_launch_pixel_proof(c->d_kp, kp.n_pixels, kp.strip_list != nullptr, stream));
-    HIPCHK(c, hipEventRecord(c->ev_main[ring], stream));
-    HIPCHK(c, rrt_launch_path(c->d_kp, waves, grid, stream));
-  } else if (pixel_loop) {
-    std::snprintf(name, sizeof(name), "%srrt_render_kernel<%s, %s, %d, ...>", deep_list ? "rrt_pixel_proof_kernel + " : "",
-                  tf[deep || sw || sky || disk], tf[count], lean == 2 ? 0 : lean);
-    if (deep_list) HIPCHK(c, rrt_launch_pixel_proof(c->d_kp, kp.n_pixels, kp.strip_list != nullptr, stream));
-    HIPCHK(c, hipEventRecord(c->ev_main[ring], stream));
-    HIPCHK(c, rrt_launch_render(kp, c->d_kp, deep, count, lean, waves, grid, stream));
-  } else {
-    std::snprintf(name, sizeof(name), "%srrt_sample_kernel<%s, %d, %d, %s>", deep_list ? "rrt_pixel_proof_kernel + " : "",
-                  tf[count], lean, deep_sample ? (waves == 2 || waves == 4 ? waves : 3) : waves, tf[deep_sample]);
-    if (deep_list) HIPCHK(c, rrt_launch_pixel_proof(c->d_kp, kp.n_pixels, kp.strip_list != nullptr, stream));
-    HIPCHK(c, hipEventRecord(c->ev_main[ring], stream));
-    HIPCHK(c, rrt_launch_sample(kp, c->d_kp, count, lean, waves, grid, stream));
-  }
-  c->last_kernel = name;
-  c->last_heavy = kp.heavy_list ? kp.heavy_cap : 0u;
-  c->last_cont = kp.cont ? kp.cont_cap : 0u;
-  HIPCHK(c, hipEventRecord(c->ev1[ring], stream));
-#if RRT_PROFILE
-  if (wd_ms > 0) {
-    const auto t_end = std::chrono::steady_clock::now() + std::chrono::milliseconds(wd_ms);
-    hipError_t q;
-    while ((q = hipEventQuery(c->ev1[ring])) == hipErrorNotReady && std::chrono::steady_clock::now() < t_end)
-      std::this_thread::sleep_for(std::chrono::milliseconds(1));
-    if (q == hipErrorNotReady) {
-      std::fprintf(stderr, "WATCHDOG: launch '%s' not done after %ld ms (grid %u, heavy list %s); live records:\n",
-                   name, wd_ms, c->last_grid, kp.heavy_list ? "on" : "off");
-      int shown = 0, live_b = 0, live_h = 0;
-      for (uint32_t w = 0; w < RRT_WD_WORDS / 4; ++w) {
-        const volatile uint32_t* r = c->h_wd + 4 * w;
-        if (r[3] == 0 || r[3] == 0xdeadu) continue;
-        if (w < RRT_WD_HEAVY / 4) ++live_b; else ++live_h;
-        if (shown++ < 64)
-          std::fprintf(stderr, "  %s %u: it %u state 0x%x pixel %u marker 0x%x\n", w < RRT_WD_HEAVY / 4 ? "wave" : "heavy",
-                       w < RRT_WD_HEAVY / 4 ? w : w - RRT_WD_HEAVY / 4, r[0], r[1], r[2], r[3]);
-      }
-      std::fprintf(stderr, "WATCHDOG: %d batch waves and %d heavy blocks not exited\n", live_b, live_h);
-      std::fflush(stderr);
-      _exit(3);
-    }
-  }
-#endif
-  c->timed = true;
-  ++c->n_launch;
-  return RRT_OK;
+  if (int rc = fill_disk_params(c, kp)) return rc;  // (check_launch has passed check_disk)
+  // the switches' build marches every ray exactly; the lensed sky's and the disk's run no proof at all
+  if (m.sw) { kp.miss.on = 0u; kp.occ.on = 0u; }
+  if (m.sky || m.disk) { kp.miss.on = 0u; kp.occ.on = 0u; kp.kproof.on = 0u; }
+  const LaunchPlan pl = plan_launch(c, p, m, proofs_valid, n_tiles, ts, kp);
+  return enqueue(c, p, m, pl, kp, tiles, n_tiles, ts, stream);
 }
 
 extern "C" int rrt_render_tiles_device(rrt_ctx* c, const rrt_render_params* p, const uint32_t* tiles,
@@ -2155,15 +2208,8 @@ extern "C" int rrt_unpack_tiles_device(rrt_ctx* c, const uint32_t* tiles, uint32
   hipStream_t s = stream ? (hipStream_t)stream : (hipStream_t)0;
   HIPCHK(c, hipSetDevice(c->device));
   if (int rc = scratch_acquire(c, s)) return rc;
-  struct FenceGuard {
-    rrt_ctx* c; hipStream_t s;
-    ~FenceGuard() { scratch_release(c, s); }
-  } fence_guard{c, s};
-  if (c->tiles_cap < n_tiles) {
-    hipFree(c->d_tiles); c->d_tiles = nullptr;
-    HIPCHK(c, hipMalloc(&c->d_tiles, sizeof(uint32_t) * 2 * n_tiles));
-    c->tiles_cap = n_tiles;
-  }
+  FenceGuard fence_guard{c, s};
+  if (int rc = grow(c, c->d_tiles, c->tiles_cap, 2 * (size_t)n_tiles)) return rc;
   HIPCHK(c, hipMemcpyAsync(c->d_tiles, tiles, sizeof(uint32_t) * 2 * n_tiles, hipMemcpyHostToDevice, s));
   HIPCHK(c, rrt_launch_unpack(c->d_tiles, n_tiles, ts, fw, fh, rgb_p, cnt_p, rgb, cnt, s));
   return RRT_OK;
@@ -2302,10 +2348,7 @@ static int trace_launch(rrt_ctx* c, const rrt_trace_params* tp, bool cam, const 
   if (((uintptr_t)d_rays | (uintptr_t)d_hits) & 15u) return fail(c, RRT_E_INVALID, "ray / hit buffers must be 16-byte aligned");
   HIPCHK(c, hipSetDevice(c->device));
   if (int rc = scratch_acquire(c, stream)) return rc;
-  struct FenceGuard {
-    rrt_ctx* c; hipStream_t s;
-    ~FenceGuard() { scratch_release(c, s); }
-  } fence_guard{c, stream};
+  FenceGuard fence_guard{c, stream};
   KParams kp{};  // proofs, audit, diagnostics and render state: all off / unused
   fill_scene_params(c, 0u, kp);
   kp.frame_w = (double)fw; kp.frame_h = (double)fh;
@@ -2337,16 +2380,6 @@ static int trace_region(rrt_ctx* c, uint32_t fw, uint32_t fh, uint32_t x0, uint3
   return RRT_OK;
 }
 
-// staging buffer of a host-buffer query (grown as needed; hipFree waits for the device)
-static int trace_stage(rrt_ctx* c, void** p, size_t& cap, size_t bytes) {
-  if (cap >= bytes) return RRT_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  hipFree(*p); *p = nullptr; cap = 0;
-  HIPCHK(c, hipMalloc(p, bytes));
-  cap = bytes;
-  return RRT_OK;
-}
-
 extern "C" int rrt_trace_rays_device(rrt_ctx* c, const rrt_trace_params* tp, const rrt_ray* d_rays, uint32_t n,
                                      rrt_hit* d_hits, void* stream) {
   if (!c) return RRT_E_INVALID;
@@ -2365,17 +2398,18 @@ extern "C" int rrt_trace_camera_device(rrt_ctx* c, const rrt_trace_params* tp, u
 static int trace_host(rrt_ctx* c, const rrt_trace_params* tp, bool cam, const rrt_ray* rays, uint32_t fw, uint32_t fh, uint32_t x0,
                       uint32_t y0, uint32_t w, uint32_t n, rrt_hit* hits) {
   const bool staged = n && c->device >= 0 && c->has_scene;
-  if (staged) {
-    if (int rc = trace_stage(c, &c->d_trace_hits, c->trace_hits_cap, sizeof(rrt_hit) * (size_t)n)) return rc;
+  if (staged) {  // the staging buffers (grow)
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = grow(c, c->d_trace_hits, c->trace_hits_cap, n)) return rc;
     if (!cam) {
-      if (int rc = trace_stage(c, &c->d_trace_rays, c->trace_rays_cap, sizeof(rrt_ray) * (size_t)n)) return rc;
+      if (int rc = grow(c, c->d_trace_rays, c->trace_rays_cap, n)) return rc;
       // (every host-buffer query ends in the synchronise below: no earlier one still reads the staging)
       HIPCHK(c, hipMemcpyAsync(c->d_trace_rays, rays, sizeof(rrt_ray) * (size_t)n, hipMemcpyHostToDevice, c->stream));
     }
   }
   // not staged: a call that fails or has nothing to do (trace_launch says which) before any buffer is used
-  if (int rc = trace_launch(c, tp, cam, staged && !cam ? (const rrt_ray*)c->d_trace_rays : nullptr, fw, fh, x0, y0, w, n,
-                            staged ? (rrt_hit*)c->d_trace_hits : nullptr, c->stream))
+  if (int rc = trace_launch(c, tp, cam, staged && !cam ? c->d_trace_rays : nullptr, fw, fh, x0, y0, w, n,
+                            staged ? c->d_trace_hits : nullptr, c->stream))
     return rc;
   if (!staged) return RRT_OK;
   HIPCHK(c, hipMemcpyAsync(hits, c->d_trace_hits, sizeof(rrt_hit) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
@@ -2414,13 +2448,13 @@ extern "C" int rrt_render(rrt_ctx* c, const rrt_render_params* p, uint32_t x0, u
     for (uint32_t tx = x0; tx < x0 + w; tx += ts) { tiles.push_back(tx); tiles.push_back(ty); }
   const uint32_t nt = (uint32_t)(tiles.size() / 2);
   const size_t npx = (size_t)nt * ts * ts;
-  if (c->px_cap < npx) {
-    size_t dummy = 0;
+  if (c->px_cap < npx) {  // the four output buffers grow together: px_cap pixels each
+    size_t cap[4] = {};
     int rc;
-    if ((rc = ensure(c, (void**)&c->d_rgb, dummy, npx, 3 * sizeof(float)))) return rc;
-    if ((rc = ensure(c, (void**)&c->d_cnt, dummy, npx, sizeof(int32_t)))) return rc;
-    if ((rc = ensure(c, (void**)&c->d_draws, dummy, npx, sizeof(uint32_t)))) return rc;
-    if ((rc = ensure(c, (void**)&c->d_ctr, dummy, npx, 4 * sizeof(uint32_t)))) return rc;
+    if ((rc = grow(c, c->d_rgb, cap[0], 3 * npx))) return rc;
+    if ((rc = grow(c, c->d_cnt, cap[1], npx))) return rc;
+    if ((rc = grow(c, c->d_draws, cap[2], npx))) return rc;
+    if ((rc = grow(c, c->d_ctr, cap[3], 4 * npx))) return rc;
     c->px_cap = npx;
   }
   rrt_render_params q = *p;

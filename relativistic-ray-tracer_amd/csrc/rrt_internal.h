@@ -32,6 +32,57 @@
 #define RRT_PATH_WAVES 4    // ... and its default register budget (waves per SIMD)
 #define RRT_BIG_REACH 10   // oversized-leaf cell masks: dilation radius in grid cells (rrt_host.cpp)
 
+// ------------------------------------------------------------------ kernel variants
+// Each variant is its own kernel build, so no build carries code (and registers) it never runs.  The
+// host chooses one per launch (rrt_host.cpp choose_variant); the integrator templates take it as an
+// int (rrt_device.h).  A new build: one constant here, one arm of choose_variant, one arm of its shim.
+namespace rrt {
+// general, Schwarzschild;  LEAN: area lights only, no microfacet BSDF, importance-sampled direct
+// light;  LEAN with point lights too (the values of the scene's LEAN class, rrt_ctx::lean)
+constexpr int V_GENERAL = 0;
+constexpr int V_LEAN = 1;
+constexpr int V_LEAN_POINT = 2;
+// general with the Kerr march
+constexpr int V_KERR = 3;
+// V_SW: the general Schwarzschild build with the reference's compile-time switches as run-time
+// flags (KParams::sw; include/rrt.h RRT_RENDER_THIN_LENS .. RRT_RENDER_ILLUM_MASK)
+constexpr int V_SW = 4;
+// V_SKY / V_KERR_SKY: the general builds with the lensed sky (RRT_SPACETIME_LENSED_SKY):
+// every query runs the exit-mode march and an escaping ray looks the environment map up along its
+// exit direction.  Per-pixel-loop kernel only (rrt_kernel.hip); no proofs.
+constexpr int V_SKY = 5;
+constexpr int V_KERR_SKY = 6;
+// V_KERR_DISK: the general Kerr build with the accretion disk (rrt_set_disk).  It carries
+// the exit-mode march and takes the lensed sky's rule or the reference's at run time (kp.disk.lensed).
+// Per-pixel-loop kernel only; no proofs.
+constexpr int V_KERR_DISK = 7;
+// V_KERR_DISK_BB: V_KERR_DISK with the blackbody colour rule (RRT_DISK_BLACKBODY) in
+// place of the plain one: a build of its own, so that V_KERR_DISK keeps its registers and scratch.
+constexpr int V_KERR_DISK_BB = 8;
+// V_KERR_DISK_LIGHT / V_KERR_DISK_BB_LIGHT: the two disk builds with the disk importance-sampled as a
+// light (RRT_DISK_LIGHT; rrt_integrator.h disk_direct): builds of their own, so that
+// their parents keep their registers and scratch.  Everywhere else they behave as their parents.
+constexpr int V_KERR_DISK_LIGHT = 9;
+constexpr int V_KERR_DISK_BB_LIGHT = 10;
+// V_KERR_DISK_PT / V_KERR_DISK_PT_LIGHT: builds 8 and 10 with the Page-Thorne temperature profile
+// (RRT_DISK_PROFILE_PAGE_THORNE) as disk_rgb's q: builds of their own, so that the log
+// chain is no run-time branch in their parents.  Everywhere else they behave as their parents.
+constexpr int V_KERR_DISK_PT = 11;
+constexpr int V_KERR_DISK_PT_LIGHT = 12;
+__host__ __device__ constexpr bool is_lean(int v) { return v == V_LEAN || v == V_LEAN_POINT; }
+__host__ __device__ constexpr bool is_sky(int v) { return v == V_SKY || v == V_KERR_SKY; }
+__host__ __device__ constexpr bool is_disk_pt(int v) { return v == V_KERR_DISK_PT || v == V_KERR_DISK_PT_LIGHT; }
+__host__ __device__ constexpr bool is_disk_light(int v) {
+  return v == V_KERR_DISK_LIGHT || v == V_KERR_DISK_BB_LIGHT || v == V_KERR_DISK_PT_LIGHT;
+}
+__host__ __device__ constexpr bool is_disk_bb(int v) { return v == V_KERR_DISK_BB || v == V_KERR_DISK_BB_LIGHT || is_disk_pt(v); }
+__host__ __device__ constexpr bool is_disk(int v) { return v == V_KERR_DISK || is_disk_bb(v) || is_disk_light(v); }
+__host__ __device__ constexpr bool is_kerr_build(int v) { return v == V_KERR || v == V_KERR_SKY || is_disk(v); }
+__host__ __device__ constexpr int general_of(int v) {  // non-LEAN build
+  return v == V_KERR || v == V_SW || is_sky(v) || is_disk(v) ? v : V_GENERAL;
+}
+}  // namespace rrt
+
 // BVH node, 64 B, left-first pre-order (the reference's recursion order, bvh.cpp:115-138).
 // Left child of an inner node is always index + 1; `skip` is the pre-order successor of the
 // whole subtree, so "bbox missed or leaf done -> skip, else -> index + 1" visits exactly the

@@ -261,33 +261,28 @@ __global__ void rrt_disk_sample_kernel(const DHole hole, const DDisk disk, uint6
 // ------------------------------------------------------------------ launch shims (C++ linkage)
 // Kernel selection: deep / counting variants are built once (1 wave per SIMD budget); the
 // depth <= 1 path has general and LEAN builds at 1..4 waves per SIMD (A/B knob `waves`).
-// lean = the kernel variant (rrt_device.h: 0 general, 1/2 LEAN, V_KERR).
-hipError_t rrt_launch_render(const KParams& kp, const KParams* d_kp, int deep, int count, int lean, int waves, uint32_t grid,
+// variant = the kernel build (rrt_internal.h V_*), as rrt_host.cpp choose_variant chose it.
+hipError_t rrt_launch_render(const KParams& kp, const KParams* d_kp, int deep, int count, int variant, int waves, uint32_t grid,
                              hipStream_t stream) {
 #define RRT_LAUNCH(D, C, L, W) hipLaunchKernelGGL((rrt_render_kernel<D, C, L, W>), dim3(grid), dim3(256), 0, stream, d_kp)
   // the bounce levels in LDS (frames of max_ray_depth <= 4; RRT_AB_NO_LEVEL_LDS=1 keeps them private, A/B)
   static const bool no_lv = [] { const char* e = std::getenv("RRT_AB_NO_LEVEL_LDS"); return e && e[0] == '1'; }();
   const bool lv4 = deep && !count && kp.max_ray_depth <= 4u && !no_lv;
-  if (lean == rrt::V_SKY) {  // the lensed sky: one bounce-capable build per metric, no counters; 2 waves/SIMD
-                             // (cfg3's framing 141.8 -> 117.4 ms against 1; the cfg5 crop the same, profiles/README.md)
-    RRT_LAUNCH(true, false, rrt::V_SKY, 2);
-  } else if (lean == rrt::V_KERR_SKY) {
-    RRT_LAUNCH(true, false, rrt::V_KERR_SKY, 2);
-  } else if (lean == rrt::V_KERR_DISK) {  // the accretion disk: one bounce-capable build, either sky rule; as V_KERR_SKY
-    RRT_LAUNCH(true, false, rrt::V_KERR_DISK, 2);
-  } else if (lean == rrt::V_KERR_DISK_BB) {  // ... with the blackbody colour: a build of its own
-    RRT_LAUNCH(true, false, rrt::V_KERR_DISK_BB, 2);
-  } else if (lean == rrt::V_KERR_DISK_LIGHT) {  // ... with the disk sampled as a light: builds of their own
-    RRT_LAUNCH(true, false, rrt::V_KERR_DISK_LIGHT, 2);
-  } else if (lean == rrt::V_KERR_DISK_BB_LIGHT) {
-    RRT_LAUNCH(true, false, rrt::V_KERR_DISK_BB_LIGHT, 2);
-  } else if (lean == rrt::V_KERR_DISK_PT) {  // builds 8 and 10 with the Page-Thorne profile
-    RRT_LAUNCH(true, false, rrt::V_KERR_DISK_PT, 2);
-  } else if (lean == rrt::V_KERR_DISK_PT_LIGHT) {
-    RRT_LAUNCH(true, false, rrt::V_KERR_DISK_PT_LIGHT, 2);
-  } else if (lean == rrt::V_SW) {  // the reference's switches as run-time flags: one bounce-capable build
+  // The lensed sky (one build per metric) and the accretion disk (plain, blackbody DESIGN.md §13, sampled
+  // as a light §14, Page-Thorne §15: builds of their own): bounce-capable, no counters, 2 waves/SIMD
+  // (cfg3's framing 141.8 -> 117.4 ms against 1; the cfg5 crop the same, profiles/README.md)
+  switch (variant) {
+#define RRT_SKY_DISK(V) case rrt::V: RRT_LAUNCH(true, false, rrt::V, 2); return hipGetLastError();
+    RRT_SKY_DISK(V_SKY) RRT_SKY_DISK(V_KERR_SKY)
+    RRT_SKY_DISK(V_KERR_DISK) RRT_SKY_DISK(V_KERR_DISK_BB)
+    RRT_SKY_DISK(V_KERR_DISK_LIGHT) RRT_SKY_DISK(V_KERR_DISK_BB_LIGHT)
+    RRT_SKY_DISK(V_KERR_DISK_PT) RRT_SKY_DISK(V_KERR_DISK_PT_LIGHT)
+#undef RRT_SKY_DISK
+    default: break;
+  }
+  if (variant == rrt::V_SW) {  // the reference's switches as run-time flags: one bounce-capable build
     if (count) RRT_LAUNCH(true, true, rrt::V_SW, 1); else RRT_LAUNCH(true, false, rrt::V_SW, 1);
-  } else if (lean == rrt::V_KERR) {  // the Kerr builds (general integrator)
+  } else if (variant == rrt::V_KERR) {  // the Kerr builds (general integrator)
     if (deep) {
       if (count) RRT_LAUNCH(true, true, rrt::V_KERR, 1); else RRT_LAUNCH(true, false, rrt::V_KERR, 1);
     } else if (count) {
@@ -313,7 +308,7 @@ hipError_t rrt_launch_render(const KParams& kp, const KParams* d_kp, int deep, i
     }
   } else if (count) {
     RRT_LAUNCH(false, true, false, 1);
-  } else if (lean == 1) {  // LEAN 2 (point lights) runs the general build here
+  } else if (variant == rrt::V_LEAN) {  // V_LEAN_POINT runs the general build here
     switch (waves) {
       case 1: RRT_LAUNCH(false, false, true, 1); break;
       case 3: RRT_LAUNCH(false, false, true, 3); break;

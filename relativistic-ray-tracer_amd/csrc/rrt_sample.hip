@@ -624,15 +624,15 @@ __global__ __launch_bounds__(64 * NW, HW) void rrt_heavy_kernel(const KParams* _
 }
 
 // waves/SIMD budget 4 or 5; NW waves per pixel (1, 2 or 4); grid in blocks; mode RRT_HEAVY_*
-hipError_t rrt_launch_heavy(const KParams* d_kp, int lean, int waves, int nw, uint32_t grid, int mode, hipStream_t stream) {
+hipError_t rrt_launch_heavy(const KParams* d_kp, int variant, int waves, int nw, uint32_t grid, int mode, hipStream_t stream) {
 #define RRT_LAUNCH_H(L, W, N) hipLaunchKernelGGL((rrt_heavy_kernel<L, W, N>), dim3(grid), dim3(64 * N), 0, stream, d_kp, mode)
-  if (lean == 1) {
+  if (variant == rrt::V_LEAN) {
     if (waves == 5) {
       if (nw == 1) RRT_LAUNCH_H(1, 5, 1); else if (nw == 4) RRT_LAUNCH_H(1, 5, 4); else RRT_LAUNCH_H(1, 5, 2);
     } else {
       if (nw == 1) RRT_LAUNCH_H(1, 4, 1); else if (nw == 4) RRT_LAUNCH_H(1, 4, 4); else RRT_LAUNCH_H(1, 4, 2);
     }
-  } else if (lean == 2) {
+  } else if (variant == rrt::V_LEAN_POINT) {
     if (nw == 4) RRT_LAUNCH_H(2, 4, 4); else RRT_LAUNCH_H(2, 4, 2);
   } else {
     return hipErrorInvalidValue;
@@ -1282,20 +1282,20 @@ __global__ __launch_bounds__(256, WAVES) void rrt_first_kernel(const KParams* __
   }
 }
 
-hipError_t rrt_launch_first(const KParams& kp, const KParams* d_kp, int lean, int waves, uint32_t grid, hipStream_t stream) {
+hipError_t rrt_launch_first(const KParams& kp, const KParams* d_kp, int variant, int waves, uint32_t grid, hipStream_t stream) {
   // waves/SIMD: 3 by default; the LEAN area-light build also at 4 / 5 (A/B)
-  if (lean == 1 && waves == 4) hipLaunchKernelGGL((rrt_first_kernel<1, 4>), dim3(grid), dim3(256), 0, stream, d_kp);
-  else if (lean == 1 && waves == 5) hipLaunchKernelGGL((rrt_first_kernel<1, 5>), dim3(grid), dim3(256), 0, stream, d_kp);
-  else if (lean == 1) hipLaunchKernelGGL((rrt_first_kernel<1, 3>), dim3(grid), dim3(256), 0, stream, d_kp);
-  else if (lean == 2) hipLaunchKernelGGL((rrt_first_kernel<2, 3>), dim3(grid), dim3(256), 0, stream, d_kp);
-  else if (lean == rrt::V_KERR) hipLaunchKernelGGL((rrt_first_kernel<rrt::V_KERR, 3>), dim3(grid), dim3(256), 0, stream, d_kp);
+  if (variant == rrt::V_LEAN && waves == 4) hipLaunchKernelGGL((rrt_first_kernel<1, 4>), dim3(grid), dim3(256), 0, stream, d_kp);
+  else if (variant == rrt::V_LEAN && waves == 5) hipLaunchKernelGGL((rrt_first_kernel<1, 5>), dim3(grid), dim3(256), 0, stream, d_kp);
+  else if (variant == rrt::V_LEAN) hipLaunchKernelGGL((rrt_first_kernel<1, 3>), dim3(grid), dim3(256), 0, stream, d_kp);
+  else if (variant == rrt::V_LEAN_POINT) hipLaunchKernelGGL((rrt_first_kernel<2, 3>), dim3(grid), dim3(256), 0, stream, d_kp);
+  else if (variant == rrt::V_KERR) hipLaunchKernelGGL((rrt_first_kernel<rrt::V_KERR, 3>), dim3(grid), dim3(256), 0, stream, d_kp);
   else hipLaunchKernelGGL((rrt_first_kernel<0, 3>), dim3(grid), dim3(256), 0, stream, d_kp);
   return hipGetLastError();
 }
 
-hipError_t rrt_launch_batch(const KParams& kp, const KParams* d_kp, int lean, int waves, uint32_t grid, hipStream_t stream) {
+hipError_t rrt_launch_batch(const KParams& kp, const KParams* d_kp, int variant, int waves, uint32_t grid, hipStream_t stream) {
 #define RRT_LAUNCH_B(L, W) hipLaunchKernelGGL((rrt_batch_kernel<L, W>), dim3(grid), dim3(256), 0, stream, d_kp)
-  if (lean == 1) {
+  if (variant == rrt::V_LEAN) {
     switch (waves) {
       case 2: RRT_LAUNCH_B(1, 2); break;
       case 3: RRT_LAUNCH_B(1, 3); break;
@@ -1303,13 +1303,13 @@ hipError_t rrt_launch_batch(const KParams& kp, const KParams* d_kp, int lean, in
       case 5: RRT_LAUNCH_B(1, 5); break;
       default: RRT_LAUNCH_B(1, 5); break;
     }
-  } else if (lean == 2) {
+  } else if (variant == rrt::V_LEAN_POINT) {
     switch (waves) {
       case 3: RRT_LAUNCH_B(2, 3); break;
       case 4: RRT_LAUNCH_B(2, 4); break;
       default: RRT_LAUNCH_B(2, 5); break;
     }
-  } else if (lean == rrt::V_KERR) {  // general builds: waves/SIMD as an A/B knob
+  } else if (variant == rrt::V_KERR) {  // general builds: waves/SIMD as an A/B knob
     switch (waves) {
       case 2: RRT_LAUNCH_B(rrt::V_KERR, 2); break;
       case 4: RRT_LAUNCH_B(rrt::V_KERR, 4); break;
@@ -1328,27 +1328,27 @@ hipError_t rrt_launch_batch(const KParams& kp, const KParams* d_kp, int lean, in
   return hipGetLastError();
 }
 
-hipError_t rrt_launch_sample(const KParams& kp, const KParams* d_kp, int count, int lean, int waves, uint32_t grid, hipStream_t stream) {
+hipError_t rrt_launch_sample(const KParams& kp, const KParams* d_kp, int count, int variant, int waves, uint32_t grid, hipStream_t stream) {
 #define RRT_LAUNCH(C, L, W) hipLaunchKernelGGL((rrt_sample_kernel<C, L, W>), dim3(grid), dim3(256), 0, stream, d_kp)
 #define RRT_LAUNCH_DEEP(W) hipLaunchKernelGGL((rrt_sample_kernel<false, 0, W, true>), dim3(grid), dim3(256), 0, stream, d_kp)
-  if (!count && kp.max_ray_depth >= 2 && lean != rrt::V_KERR) {  // bounce paths, general build
+  if (!count && kp.max_ray_depth >= 2 && variant != rrt::V_KERR) {  // bounce paths, general build
     switch (waves) {
       case 2: RRT_LAUNCH_DEEP(2); break;
       case 4: RRT_LAUNCH_DEEP(4); break;
       default: RRT_LAUNCH_DEEP(3); break;
     }
   } else if (count) {
-    if (lean == rrt::V_KERR) RRT_LAUNCH(true, rrt::V_KERR, 1); else RRT_LAUNCH(true, 0, 1);
-  } else if (lean == rrt::V_KERR) {
+    if (variant == rrt::V_KERR) RRT_LAUNCH(true, rrt::V_KERR, 1); else RRT_LAUNCH(true, 0, 1);
+  } else if (variant == rrt::V_KERR) {
     RRT_LAUNCH(false, rrt::V_KERR, 2);
-  } else if (lean == 1) {
+  } else if (variant == rrt::V_LEAN) {
     switch (waves) {
       case 2: RRT_LAUNCH(false, 1, 2); break;
       case 4: RRT_LAUNCH(false, 1, 4); break;
       case 5: RRT_LAUNCH(false, 1, 5); break;
       default: RRT_LAUNCH(false, 1, 3); break;
     }
-  } else if (lean == 2) {
+  } else if (variant == rrt::V_LEAN_POINT) {
     RRT_LAUNCH(false, 2, 3);
   } else {
     RRT_LAUNCH(false, false, 2);

@@ -6,7 +6,7 @@ TEST INFRASTRUCTURE ONLY (tests/test_miss_proof.py): the product runs the HIP ve
 The proof replaces the reference's march (blackhole.cpp:17-40, bvh.cpp:103-113) for a camera ray
 by the planar recurrence it follows in exact arithmetic and accepts "miss" only when every
 segment of the recurrence clears the root box by a margin far above the recurrence's deviation
-from the reference's floating-point march.  Constants as rrt_host.cpp launch() sets them.
+from the reference's floating-point march.  Constants as rrt_host.cpp fill_proof_params sets them.
 """
 import numpy as np
 
