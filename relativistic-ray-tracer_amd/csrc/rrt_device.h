@@ -49,6 +49,47 @@ __device__ __forceinline__ const RRT_CONST_AS T* uniform_ptr(const RRT_CONST_AS 
   return (const RRT_CONST_AS T*)(((uint64_t)hi << 32) | lo);
 }
 
+// Launch constants by stage.  KParams is a const __restrict__ kernel argument, so every
+// field a kernel reads anywhere is loop-invariant: its load is hoisted to the kernel's entry, stays live
+// through the persistent loop and, once the SGPRs run out, is spilled to VGPR lanes and comes back by
+// v_readlane -- a VALU instruction -- inside the march and walk loops.  Behind the empty asm the
+// pointer is no longer known to be the kernel argument: the fields read through the result are
+// loaded again, by s_load, where they are used, and are live only from there on.
+// Only a constant may be re-read this way: the scalar cache is not coherent with stores made during
+// a launch.  The KParams block itself is written before the launch and never during
+// it, so every field of it qualifies; what its RRT_GLOBAL_AS pointers point to (block_counter,
+// claim_count, heavy_count, cont_ctl, the lists, the continuation records, every output) does not,
+// and is still read through those pointers by global loads and atomics exactly as before.
+__device__ __forceinline__ const RRT_CONST_AS KParams* kp_renew(const RRT_CONST_AS KParams* q) {
+  asm volatile("" : "+s"(q));
+  return q;
+}
+__device__ __forceinline__ const KParams& kp_fresh(const KParams& kp) {
+  return *(const KParams*)kp_renew((const RRT_CONST_AS KParams*)&kp);
+}
+// A `const KParams&` that a persistent loop can renew at its stage boundaries (SCOPED: by its address
+// space; else the kernel argument itself, with everything the compiler knows about it)
+template <bool SCOPED>
+struct KpRef {
+  using Ptr = const RRT_CONST_AS KParams*;
+  Ptr q;
+  __device__ __forceinline__ const KParams& operator*() const { return *(const KParams*)q; }
+  __device__ __forceinline__ const KParams* operator->() const { return (const KParams*)q; }
+};
+template <>
+struct KpRef<false> {
+  using Ptr = const KParams*;
+  Ptr q;
+  __device__ __forceinline__ const KParams& operator*() const { return *q; }
+  __device__ __forceinline__ const KParams* operator->() const { return q; }
+};
+// SCOPED builds (the LEAN batch and heavy kernels) take fresh constants at a stage's start
+template <bool SCOPED>
+__device__ __forceinline__ const KParams& kp_stage(const KParams& kp) {
+  if (SCOPED) return kp_fresh(kp);
+  return kp;
+}
+
 // ------------------------------------------------------------------ Vector3D (double)
 struct v3 { double x, y, z; };
 __device__ __forceinline__ v3 V(double x, double y, double z) { v3 r; r.x = x; r.y = y; r.z = z; return r; }
@@ -792,12 +833,16 @@ __device__ __forceinline__ void next_micro(const DHole& h, v3& o, v3& d, double&
 // any_rt: a shadow query chosen at run time (the path pool kernel's rays share one query call)
 // The walk of a segment that passed the skips (segment_query); cell: its start's grid cell or -1.
 // W4: the 4-wide walk may run (query's W4; the Kerr march walks the binary tree only)
-template <bool ANY, bool COUNT, bool W4 = true>
-__device__ __forceinline__ bool segment_walk(const KParams& kp, v3 o, v3 d, double max_t, v3 e, int cell,
+// SCOPED: the shipped LEAN batch / heavy builds -- the walk's constants are read here, at its start,
+// not carried through the march (kp_stage), and the run-time diagnostics below are not compiled in
+// (launches that set a diagnostic flag take the per-sample kernel, rrt_host.cpp plan_launch)
+template <bool ANY, bool COUNT, bool W4 = true, bool SCOPED = false>
+__device__ __forceinline__ bool segment_walk(const KParams& kp_in, v3 o, v3 d, double max_t, v3 e, int cell,
                                              Isect* is, Counters& cn, bool any_rt = false, QRec* qr = nullptr) {
+  const KParams& kp = kp_stage<SCOPED>(kp_in);
   // oversized leaves with no primitive within reach of a short segment are not offered
   const uint64_t bmask = (kp.big_mask && cell >= 0 && max_t < kp.big_reach) ? (uint64_t)kp.big_mask[cell] : ~0ull;
-  if (!COUNT && kp.diag) {  // diagnostics: skip all / interior-start / exterior-start walks
+  if (!SCOPED && !COUNT && kp.diag) {  // diagnostics: skip all / interior-start / exterior-start walks
     const bool in = o.x >= kp.nodes[0].mn[0] && o.x <= kp.nodes[0].mx[0] && o.y >= kp.nodes[0].mn[1] &&
                     o.y <= kp.nodes[0].mx[1] && o.z >= kp.nodes[0].mn[2] && o.z <= kp.nodes[0].mx[2];
     if ((kp.diag & 1) || ((kp.diag & 4) && in) || ((kp.diag & 8) && !in)) return false;
@@ -847,7 +892,7 @@ __device__ __forceinline__ bool segment_walk(const KParams& kp, v3 o, v3 d, doub
   }
   return true;
 }
-template <bool ANY, bool COUNT, bool W4 = true>
+template <bool ANY, bool COUNT, bool W4 = true, bool SCOPED = false>
 __device__ __forceinline__ bool segment_query(const KParams& kp, v3 o, v3 d, double max_t, v3 e, Isect* is,
                                               Counters& cn, bool any_rt = false, QRec* qr = nullptr) {
   // e = o + d * max_t.  COUNT && kp.count_exec: count the work this path executes (grid / root
@@ -856,7 +901,7 @@ __device__ __forceinline__ bool segment_query(const KParams& kp, v3 o, v3 d, dou
   if (opt && segment_outside_root(kp, o, e)) return false;  // root test fails
   const int cell = opt ? grid_cell(kp.grid, o) : -1;
   if (cell_clear(kp.grid, cell, max_t)) return false;  // no primitive within reach
-  return segment_walk<ANY, COUNT, W4>(kp, o, d, max_t, e, cell, is, cn, any_rt, qr);
+  return segment_walk<ANY, COUNT, W4, SCOPED>(kp, o, d, max_t, e, cell, is, cn, any_rt, qr);
 }
 
 // ------------------------------------------------------------------ kernel variants
@@ -1511,9 +1556,11 @@ __device__ __forceinline__ bool shadow_occluded_proof(const KParams& kp, v3 o, v
 // DISK (Kerr exit-mode builds): the march tests the accretion disk too (kerr_march; *dk); BB: its
 // colour is the blackbody rule's; PT: with the Page-Thorne profile
 template <bool ANY, bool COUNT, bool KERR = false, bool W4 = true, bool EXIT = false, bool DISK = false, bool BB = false,
-          bool PT = false>
-RRT_QUERY_ATTR bool query(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn, bool any_rt = false,
+          bool PT = false, bool SCOPED = false>
+RRT_QUERY_ATTR bool query(const KParams& kp_in, v3 o, v3 d, Isect* is, Counters& cn, bool any_rt = false,
                           QRec* qr = nullptr, ExitRec* xr = nullptr, DiskRec* dk = nullptr) {
+  // SCOPED: the march's constants (the hole, the root box, the grid) are read at the march's start
+  const KParams& kp = kp_stage<SCOPED && !KERR>(kp_in);
   if (KERR && EXIT) return kerr_march<ANY, COUNT, true, DISK, BB, PT>(kp, o, d, is, cn, qr, xr, dk);
   if (KERR) return qr ? kerr_march<ANY, COUNT>(kp, o, d, is, cn, qr) : query_kerr<ANY, COUNT>(kp, o, d, is, cn);
   if (qr) qr->steps = (uint32_t)kp.hole.steps;  // all marched, unless a segment below ends the march
@@ -1541,7 +1588,7 @@ RRT_QUERY_ATTR bool query(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn
       return false;
     }
     e = o + vmul(d, max_t);
-    if (segment_query<ANY, COUNT, W4>(kp, o, d, max_t, e, is, cn, any_rt, qr)) {
+    if (segment_query<ANY, COUNT, W4, SCOPED>(kp, o, d, max_t, e, is, cn, any_rt, qr)) {
       RRT_QACC(tq0);
       if (qr) qr->steps = (uint32_t)j + 1u;
       return true;
@@ -1868,12 +1915,13 @@ __device__ __forceinline__ bool pixel_heavy(const KParams& kp, uint32_t px, uint
 // allocates the callee's count.  Measured on cfg3 (profiles/r02_ab_log.md): inline 31.5 ms, face
 // test out of line 31.3, whole proof out of line 37.6 (the call's frame and SGPR saves), no proof
 // 35.3.
-template <bool ANY, bool COUNT, bool KERR = false, int W = 0, bool W4 = true>
+template <bool ANY, bool COUNT, bool KERR = false, int W = 0, bool W4 = true, bool SCOPED = false>
 __device__ __forceinline__ bool query_nx(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn) {
   // shadow rays: the occlusion proof first (Schwarzschild; never in the reference-work counts)
   if (W && ANY && !KERR && kp.occ.on && !(COUNT && !kp.count_exec)) {
     RRT_T0(tp0);
-    const bool occluded = shadow_occluded_proof<W>(kp, o, d, kp.hole.steps);
+    const KParams& kq = kp_stage<SCOPED>(kp);  // the proof's constants: live inside it only
+    const bool occluded = shadow_occluded_proof<W>(kq, o, d, kq.hole.steps);
     RRT_ACC(t_squery, tp0);
     if (occluded) {
       if (COUNT && kp.audit && audit_pick(kp, o, d)) {
@@ -1883,7 +1931,7 @@ __device__ __forceinline__ bool query_nx(const KParams& kp, v3 o, v3 d, Isect* i
       return true;
     }
   }
-  return query<ANY, COUNT, KERR, W4>(kp, o, d, is, cn);
+  return query<ANY, COUNT, KERR, W4, false, false, false, false, SCOPED>(kp, o, d, is, cn);
 }
 
 // ------------------------------------------------------------------ BSDFs (bsdf.cpp / bsdf.h)

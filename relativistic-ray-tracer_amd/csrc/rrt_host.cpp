@@ -1889,8 +1889,12 @@ static LaunchPlan plan_launch(const rrt_ctx* c, const rrt_render_params* p, cons
   // (rrt_path.hip: one ray per lane per round, the paths' integrator state between rays in LDS), an A/B
   // variant: m3 269 ms at 3 waves/SIMD vs 172 ms for the per-pixel loop.
   const bool pixel_loop = !m.path_pool && ((m.deep && !pl.deep_sample) || (flags & RRT_RENDER_PIXEL_LOOP) || m.sw || m.sky || m.disk);
+  // The walk-skipping diagnostics (RRT_RENDER_DIAG_NO_*) are compiled into the per-sample and per-pixel-loop
+  // kernels only: the batch and heavy kernels' per-segment path does not carry their branch (rrt_device.h
+  // segment_walk, SCOPED), so a launch that sets one takes the per-sample kernel.
+  const bool diag_walks = (flags & (RRT_RENDER_DIAG_NO_INTERIOR | RRT_RENDER_DIAG_NO_EXTERIOR | RRT_RENDER_DIAG_NO_TRAVERSE)) != 0;
   const bool batch = !m.deep && !m.count && !pixel_loop && std::min(p->ns_aa, p->samples_per_batch) >= 5 &&
-                     !(flags & RRT_RENDER_PER_PIXEL);
+                     !(flags & RRT_RENDER_PER_PIXEL) && !diag_walks;
   pl.family = batch ? Family::Batch : m.path_pool ? Family::PathPool : pixel_loop ? Family::PixelLoop : Family::PerSample;
   pl.variant = choose_variant(c, p, m, kp.disk);
   // bounce builds: 3 waves/SIMD (m3 A/B, profiles/r03_ab_deep.jsonl: 363 / 263 / 180 / 180 ms at 1 / 2 / 3 / 4)

@@ -47,7 +47,8 @@ __device__ __forceinline__ void park_hit(RRT_LDS SL& cl, uint32_t t, const Isect
 // estimate_direct_lighting_importance (part1_code.cpp:33-57) for the hit parked in LDS
 // (park_hit), re-read per light sample so no hit state stays live across the shadow queries.
 // W: the calling kernel build's tag for the out-of-line occlusion proof (rrt_device.h query_nx)
-template <bool COUNT, int LEAN, int W = 0, class SL = ShadeLds>
+// SCOPED: the LEAN batch / heavy builds' shadow queries (rrt_device.h kp_stage)
+template <bool COUNT, int LEAN, int W = 0, class SL = ShadeLds, bool SCOPED = false>
 __device__ __forceinline__ spec direct_importance_parked(const KParams& kp, Rng& g, RRT_LDS SL& cl, uint32_t t, Counters& cn) {
   const uint32_t bsdf = lget(cl.bsdf, t);
   spec L = S(0, 0, 0);
@@ -68,7 +69,7 @@ __device__ __forceinline__ spec direct_importance_parked(const KParams& kp, Rng&
       const spec contrib = ((sample * bsdf_f<LEAN>(kp.bsdfs[bsdf], to_local(f, wo), w_in)) * (float)w_in.z) / pdf;
       // only the loop state and the RNG stay in registers across the shadow query
       lput(cl.cr, t, contrib.r); lput(cl.cg, t, contrib.g); lput(cl.cb, t, contrib.b);
-      if (!query_nx<true, COUNT, LEAN == V_KERR, W, is_lean(LEAN)>(kp, hp + smul(EPS_D, wi_world), wi_world, nullptr, cn))
+      if (!query_nx<true, COUNT, LEAN == V_KERR, W, is_lean(LEAN), SCOPED>(kp, hp + smul(EPS_D, wi_world), wi_world, nullptr, cn))
         L = L + S(lget(cl.cr, t), lget(cl.cg, t), lget(cl.cb, t));
     }
   }
@@ -513,15 +514,15 @@ __device__ __noinline__ void heavy_pixel_block(const RRT_CONST_AS KParams* kpq, 
     const v3 w = (smul(vx, ld3(cam.c2w0)) + smul(vy, ld3(cam.c2w1))) + smul(-1.0, ld3(cam.c2w2));
     const v3 wd = unit(w);
     Isect is;
-    const bool hit = t < lim && !camera_proven_miss<false, false>(kp, ld3(cam.pos), wd, cn) &&
-                     query_nx<false, false, false>(kp, ld3(cam.pos), wd, &is, cn);
+    const bool hit = t < lim && !camera_proven_miss<false, false>(kp_fresh(kp), ld3(cam.pos), wd, cn) &&
+                     query_nx<false, false, false, 0, true, true>(kp, ld3(cam.pos), wd, &is, cn);
     spec s = S(0, 0, 0);
     if (hit) {
       park_hit(sh, t, is);
       g.ctr = sl * Dm + Dm;
       const spec e = emission(kp.bsdfs[lget(sh.bsdf, t)]);
       if (kp.max_ray_depth == 0) s = e;
-      else s = e + direct_importance_parked<false, LEAN, W>(kp, g, sh, t, cn);
+      else s = e + direct_importance_parked<false, LEAN, W, ShadeLdsN<64 * NW>, true>(kp, g, sh, t, cn);
     }
     const uint64_t hb = __ballot(hit);
     if ((t & 63u) == 0) hs.hits[t >> 6] = hb;
@@ -670,8 +671,18 @@ __device__ __forceinline__ void cont_wave_done(const KParams& kp, uint32_t lane)
 
 template <int LEAN, int WAVES>
 __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __restrict__ kpp) {
-  const KParams& kp = *kpp;
   using namespace rrt;
+  // The launch constants, renewed at the persistent loop's stage boundaries in the LEAN builds
+  // (stage(): claim, camera rounds, `lost` re-query, shading, fold), so that only a stage's own
+  // constants are live across its loops (rrt_device.h kp_renew; by its address space, as behind the
+  // asm the pointer is no longer known to be the kernel argument).  Only the KParams block is
+  // re-read; block_counter, claim_count, heavy_count, cont_ctl, the lists, the continuation
+  // records and every output are read through its RRT_GLOBAL_AS pointers as before.
+  constexpr bool SC = is_lean(LEAN);
+  KpRef<SC> kp{(typename KpRef<SC>::Ptr)kpp};
+  auto stage = [&]() {  // (from the argument each time: always in SGPRs)
+    if constexpr (SC) kp.q = kp_renew((const RRT_CONST_AS KParams*)kpp);
+  };
   __shared__ ShadeLds cl_mem;
   RRT_LDS ShadeLds& cl = lds_of(cl_mem);
   constexpr uint32_t RRT_SLOTS = SlotWindow<LEAN>::n;
@@ -685,13 +696,12 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
   RRT_LDS float* const fb = cl.cb;
   const uint32_t t = threadIdx.x;
   const uint32_t lane = t & 63u;
-  const uint32_t G = kp.group;
+  const uint32_t G = kp->group;
   const uint32_t gl = lane & (G - 1u);
   const uint32_t gbase = lane - gl;
   const uint32_t gid = t / G;  // group slot in GroupLds
-  const uint32_t ts = kp.tile_size, tpix = ts * ts;
-  const uint32_t Dm = kp.draws_miss, Dh = kp.draws_hit;
-  const DCamera& cam = kp.cam;
+  const uint32_t ts = kp->tile_size, tpix = ts * ts;
+  const uint32_t Dm = kp->draws_miss, Dh = kp->draws_hit;
   Counters cn = {};
 #if RRT_PROFILE
   const uint64_t t_start = clock64(), w_start = wall_clock64();
@@ -704,21 +714,21 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
   // need, in batch blocks of 4 waves -- leave at once, so the heavy kernel's blocks take their
   // slots whichever kernel the hardware dispatched first.  A launch with no heavy pixels keeps
   // every block (the heavy kernel's blocks then start at its end and find the list empty).
-  // With continuations the heavy blocks wait for work the whole launch: kp.cont_room blocks at least.
-  if (kp.heavy_grid) {
-    const uint32_t nh = min(*kp.heavy_count, kp.heavy_cap);
-    const uint32_t need = max((min(nh, kp.heavy_grid) * kp.heavy_nw + 3u) / 4u, kp.cont_room);
+  // With continuations the heavy blocks wait for work the whole launch: kp->cont_room blocks at least.
+  if (kp->heavy_grid) {
+    const uint32_t nh = min(*kp->heavy_count, kp->heavy_cap);
+    const uint32_t need = max((min(nh, kp->heavy_grid) * kp->heavy_nw + 3u) / 4u, kp->cont_room);
     if (blockIdx.x + min(need, gridDim.x - 1u) >= gridDim.x) {
-      cont_wave_done(kp, lane);
+      cont_wave_done(*kp, lane);
       return;
     }
   }
   bool have = false, done = false;
-  uint32_t q = blockIdx.x % kp.n_queues, q_left = kp.n_queues;  // claim queue (group leaders)
+  uint32_t q = blockIdx.x % kp->n_queues, q_left = kp->n_queues;  // claim queue (group leaders)
 
   uint64_t t_claim = 0;  // when the group claimed its pixel (wall clock)
 #if RRT_PROFILE
-  volatile uint32_t* wd = kp.wd ? kp.wd + 4u * ((blockIdx.x * (blockDim.x >> 6) + (t >> 6)) & 0x7fffu) : nullptr;
+  volatile uint32_t* wd = kp->wd ? kp->wd + 4u * ((blockIdx.x * (blockDim.x >> 6) + (t >> 6)) & 0x7fffu) : nullptr;
   uint32_t wd_it = 0;
 #endif
 
@@ -727,6 +737,7 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
     if (wd && lane == 0) { wd[0] = ++wd_it; wd[1] = (have ? 1u : 0u) | (done ? 2u : 0u); wd[3] = 0x21u; }
 #endif
     // ---- claim a pixel (one atomic per group)
+    stage();
     RRT_T0(tc0);
     // The wave's group leaders that need a pixel claim together: one atomic takes as many
     // consecutive claims as there are leaders (2 with the BASELINE group size), lane 0 issues it.
@@ -734,8 +745,8 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
     if (needers) {
       // claim space: every pixel slot, or the pixel proof's list padded to whole stripes (the
       // padding claims no pixel); read here, not held through the kernel
-      const uint32_t n_list = kp.claim_list ? *kp.claim_count + (kp.claim_back ? kp.claim_count[1] : 0u) : 0u;
-      const uint32_t npx = kp.claim_list ? (n_list + STRIPE - 1) / STRIPE * STRIPE : kp.n_pixels;
+      const uint32_t n_list = kp->claim_list ? *kp->claim_count + (kp->claim_back ? kp->claim_count[1] : 0u) : 0u;
+      const uint32_t npx = kp->claim_list ? (n_list + STRIPE - 1) / STRIPE * STRIPE : kp->n_pixels;
       uint64_t pending = needers;
       uint32_t p = npx + 1;  // npx + 1: this group did not claim
       while (pending) {
@@ -747,11 +758,11 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
           } else {
             // striped queues: queue q holds the runs q, q + nq, q + 2 nq, ... of STRIPE
             // consecutive claims (n_pixels is a multiple of 64: tiles of 8k x 8k pixels)
-            const uint32_t nq = kp.n_queues;
-            const uint32_t qb = kp.q_stripe ? 0u : (q ? kp.q_end[q - 1] : 0u);
-            const uint32_t qn = kp.q_stripe ? (npx / STRIPE - q + nq - 1) / nq * STRIPE
-                                            : (kp.claim_list ? npx : kp.q_end[q] - qb);
-            const uint32_t k = atomicAdd(kp.block_counter + RRT_QUEUE_STRIDE * q, want);
+            const uint32_t nq = kp->n_queues;
+            const uint32_t qb = kp->q_stripe ? 0u : (q ? kp->q_end[q - 1] : 0u);
+            const uint32_t qn = kp->q_stripe ? (npx / STRIPE - q + nq - 1) / nq * STRIPE
+                                            : (kp->claim_list ? npx : kp->q_end[q] - qb);
+            const uint32_t k = atomicAdd(kp->block_counter + RRT_QUEUE_STRIDE * q, want);
             if (k < qn) {
               base = qb + k; got = min(want, qn - k); qc = q;
             } else if (--q_left == 0) {
@@ -766,7 +777,7 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
         const bool mine = (pending >> gbase) & 1ull;
         if (mine && rank < got) {
           const uint32_t ix = base + rank;
-          p = kp.q_stripe ? ((ix / STRIPE) * kp.n_queues + qc) * STRIPE + ix % STRIPE : ix;
+          p = kp->q_stripe ? ((ix / STRIPE) * kp->n_queues + qc) * STRIPE + ix % STRIPE : ix;
         }
         if (mine && out) p = npx;
         pending = out ? 0ull : (got >= want ? 0ull : pending & ~__ballot(gl == 0 && mine && rank < got));
@@ -787,22 +798,22 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
 #endif
         // a list entry: pixel claim index | hint << 31 (rrt_pixel_proof_kernel)
         // (claim_back: the front part's entries, then the back part's from the list's end)
-        const uint32_t n_front = kp.claim_list ? *kp.claim_count : 0u;
-        const uint32_t ent = !kp.claim_list ? p
-                             : p < n_front ? kp.claim_list[p]
-                             : p < n_list ? kp.claim_list[kp.claim_back ? kp.n_pixels - 1u - (p - n_front) : p]
-                             : kp.n_pixels;
-        const uint32_t ix = kp.claim_list ? (ent & 0x7fffffffu) : ent;
-        const uint32_t pi = ix < kp.n_pixels ? ix : 0u;
-        const uint32_t tl = kp.tile_order[pi / tpix], r = claim_r(pi % tpix, ts), lx = r % ts, ly = r / ts;
-        const uint32_t x = kp.tiles[2 * tl] + lx, y = kp.tiles[2 * tl + 1] + ly;
-        if (ix < kp.n_pixels && x >= kp.clip_x0 && y >= kp.clip_y0 && x < kp.clip_x1 && y < kp.clip_y1) {
+        const uint32_t n_front = kp->claim_list ? *kp->claim_count : 0u;
+        const uint32_t ent = !kp->claim_list ? p
+                             : p < n_front ? kp->claim_list[p]
+                             : p < n_list ? kp->claim_list[kp->claim_back ? kp->n_pixels - 1u - (p - n_front) : p]
+                             : kp->n_pixels;
+        const uint32_t ix = kp->claim_list ? (ent & 0x7fffffffu) : ent;
+        const uint32_t pi = ix < kp->n_pixels ? ix : 0u;
+        const uint32_t tl = kp->tile_order[pi / tpix], r = claim_r(pi % tpix, ts), lx = r % ts, ly = r / ts;
+        const uint32_t x = kp->tiles[2 * tl] + lx, y = kp->tiles[2 * tl + 1] + ly;
+        if (ix < kp->n_pixels && x >= kp->clip_x0 && y >= kp->clip_y0 && x < kp->clip_x1 && y < kp->clip_y1) {
           if (gl == 0) {
             const uint32_t slot = tl * tpix + r;
             lput(gs.px, gid, x); lput(gs.py, gid, y); lput(gs.slot, gid, slot);
-            lput(gs.key, gid, rrt_pixel_key(kp.seed, x, y));
-            if (kp.first) {  // sample 0 from rrt_first_kernel; its hit status is the hypothesis
-              const KParams::FirstSample f0 = kp.first[slot];
+            lput(gs.key, gid, rrt_pixel_key(kp->seed, x, y));
+            if (kp->first) {  // sample 0 from rrt_first_kernel; its hit status is the hypothesis
+              const KParams::FirstSample f0 = kp->first[slot];
               const spec s0 = S(f0.r, f0.g, f0.b);
               const spec ret = S(0, 0, 0) + s0;
               const double il = illum(s0);
@@ -815,7 +826,7 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
               // pixel (one whose camera rays are not all proven misses) the list entry's hint (its
               // central ray is no proven miss).  A/B: "miss" / "hit" / hint for every listed pixel:
               // cfg3 23.9 / 22.6 / 20.5 ms, cfg4 - / 19.8 / 20.1
-              const uint32_t hyp0 = !kp.claim_list ? 0u : (ent >> 31);
+              const uint32_t hyp0 = !kp->claim_list ? 0u : (ent >> 31);
               lput(gs.hyp, gid, hyp0);
               lput(gs.rr, gid, 0.0f); lput(gs.rg, gid, 0.0f); lput(gs.rb, gid, 0.0f);
               lput(gs.s1, gid, 0.0); lput(gs.s2, gid, 0.0);
@@ -831,14 +842,15 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
     }
     RRT_ACC(t_claim, tc0);
     if (__ballot(!done) == 0) break;
+    stage();  // camera rounds: none of the claim's scalars stays live through the queries
     // Tail latency: a pixel whose rounds are long (the costliest ones -- long walks next to the
     // hole and the geometry) keeps its wave busy long after the claim queue runs dry.  A wave
     // whose oldest pixel has been running for a while takes issue priority over the other waves
     // of its SIMD, so the costliest pixels finish early instead of forming the frame's tail.
     auto tail_prio = [&]() {
       const uint64_t age = have ? wall_clock64() - t_claim : 0;
-      if (__ballot(age > 4ull * kp.prio_ticks)) __builtin_amdgcn_s_setprio(3);
-      else if (__ballot(age > kp.prio_ticks)) __builtin_amdgcn_s_setprio(2);
+      if (__ballot(age > 4ull * kp->prio_ticks)) __builtin_amdgcn_s_setprio(3);
+      else if (__ballot(age > kp->prio_ticks)) __builtin_amdgcn_s_setprio(2);
       else __builtin_amdgcn_s_setprio(0);
     };
     tail_prio();
@@ -856,8 +868,8 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
     // mixed ones two or three.  A chain that leaves the slot window ends the step early (the
     // next step continues it).
     const int done_i = (int)lget(gs.i, gid);
-    const int to_check = (int)kp.samples_per_batch - done_i % (int)kp.samples_per_batch;
-    const int left = min((int)kp.ns_aa - done_i, to_check);
+    const int to_check = (int)kp->samples_per_batch - done_i % (int)kp->samples_per_batch;
+    const int left = min((int)kp->ns_aa - done_i, to_check);
     const uint32_t S1 = Dh / Dm;  // slots a hit consumes
     const uint32_t O0 = lget(gs.O, gid);
     for (uint32_t m = gl; m < RRT_SLOTS; m += G) lput(&gs.sst[gid][0], m, (uint8_t)0);
@@ -871,15 +883,17 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
     }
     // the camera query of slot sl (Camera::generate_ray, part1_code.cpp:182-187, at its jitter)
     auto slot_query = [&](uint32_t sl, Isect* is) -> bool {
+      const DCamera& cam = kp->cam;
       Rng g; g.key = lget(gs.key, gid); g.ctr = O0 + sl * Dm;
       double jx, jy; g.grid(jx, jy);
       const double sx = (double)lget(gs.px, gid) + jx, sy = (double)lget(gs.py, gid) + jy;
-      const double cx = sx / kp.frame_w, cy = sy / kp.frame_h;
+      const double cx = sx / kp->frame_w, cy = sy / kp->frame_h;
       const double vx = (1 - cx) * cam.blx + cx * -cam.blx, vy = (1 - cy) * cam.bly + cy * -cam.bly;
       const v3 w = (smul(vx, ld3(cam.c2w0)) + smul(vy, ld3(cam.c2w1))) + smul(-1.0, ld3(cam.c2w2));
       const v3 wd = unit(w);
-      if (camera_proven_miss<false, LEAN == V_KERR>(kp, ld3(cam.pos), wd, cn)) return false;
-      return query_nx<false, false, LEAN == V_KERR, 0, is_lean(LEAN)>(kp, ld3(cam.pos), wd, is, cn);
+      // (the miss proof's constants are live inside it only; query renews its own)
+      if (camera_proven_miss<false, LEAN == V_KERR>(kp_stage<SC>(*kp), ld3(cam.pos), wd, cn)) return false;
+      return query_nx<false, false, LEAN == V_KERR, 0, is_lean(LEAN), SC>(*kp, ld3(cam.pos), wd, is, cn);
     };
     const uint64_t gmask = (G >= 64 ? ~0ull : ((1ull << G) - 1ull)) << gbase;  // this group's lanes
     const uint64_t lt = ((1ull << lane) - 1ull) & gmask;                         // group lanes before me
@@ -895,6 +909,7 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
 #endif
       if (__ballot(need) == 0) break;
       if (round > 0) tail_prio();
+      stage();
 #if RRT_PROFILE
       ++prof_samples;
       ++px_rounds;
@@ -970,6 +985,7 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
     const bool act = have && (int)gl < n_step;
     const bool hit = act && hk;
     const uint32_t off = O0 + mk * Dm;
+    stage();  // `lost` re-query
     {  // move each hit sample's record into its own lane's ShadeLds slot (recompute a given-up one)
       const bool lost = hit && lget(&gs.sst[gid][0], mk) == 3;
       const uint32_t src = (t - gl) + lget(&gs.sown[gid][0], mk);
@@ -994,23 +1010,25 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
 
     // ---- shading (est_radiance_global_illumination, :103-123), all samples in parallel
     RRT_T0(ts0);
+    stage();
     spec s = S(0, 0, 0);
-    if (!is_lean(LEAN) && act && !hit && kp.env.w) {  // miss: envLight->sample_dir of the unbent camera ray
+    if (!is_lean(LEAN) && act && !hit && kp->env.w) {  // miss: envLight->sample_dir of the unbent camera ray
+      const DCamera& cam = kp->cam;
       Rng g; g.key = lget(gs.key, gid); g.ctr = off;  // re-derive the ray from its jitter draws
       double jx, jy; g.grid(jx, jy);
       const double sx = (double)lget(gs.px, gid) + jx, sy = (double)lget(gs.py, gid) + jy;
-      const double cx = sx / kp.frame_w, cy = sy / kp.frame_h;
+      const double cx = sx / kp->frame_w, cy = sy / kp->frame_h;
       const double vx = (1 - cx) * cam.blx + cx * -cam.blx, vy = (1 - cy) * cam.bly + cy * -cam.bly;
       const v3 w = (smul(vx, ld3(cam.c2w0)) + smul(vy, ld3(cam.c2w1))) + smul(-1.0, ld3(cam.c2w2));
-      s = env_dir(kp.env, unit(w));
+      s = env_dir(kp->env, unit(w));
     }
     if (act && hit) {
       Rng g; g.key = lget(gs.key, gid); g.ctr = off + Dm;
-      const spec e = emission(kp.bsdfs[lget(cl.bsdf, t)]);
-      if (kp.max_ray_depth == 0) s = e;
-      else if (is_lean(LEAN)) s = e + direct_importance_parked<false, LEAN, RRT_OCC_TAG(LEAN, WAVES)>(kp, g, cl, t, cn);
-      else if (kp.direct_hemisphere) s = e + direct_hemisphere_parked<false, LEAN>(kp, g, cl, t, cn);
-      else s = e + direct_importance_parked<false, LEAN, RRT_OCC_TAG(LEAN, WAVES)>(kp, g, cl, t, cn);
+      const spec e = emission(kp->bsdfs[lget(cl.bsdf, t)]);
+      if (kp->max_ray_depth == 0) s = e;
+      else if (is_lean(LEAN)) s = e + direct_importance_parked<false, LEAN, RRT_OCC_TAG(LEAN, WAVES), ShadeLds, SC>(*kp, g, cl, t, cn);
+      else if (kp->direct_hemisphere) s = e + direct_hemisphere_parked<false, LEAN>(*kp, g, cl, t, cn);
+      else s = e + direct_importance_parked<false, LEAN, RRT_OCC_TAG(LEAN, WAVES)>(*kp, g, cl, t, cn);
     }
     if (act) { lput(fr, t, s.r); lput(fg, t, s.g); lput(fb, t, s.b); }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1019,6 +1037,7 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
 
     RRT_ACC(t_shade, ts0);
     // ---- ordered fold by the group leader (raytrace_pixel's loop body, :136-158)
+    stage();
     RRT_T0(tf0);
     uint32_t stop = 0;
 #if RRT_PROFILE
@@ -1047,14 +1066,14 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
       const uint32_t nh = (uint32_t)__popcll(hm);
       const uint32_t O = lget(gs.O, gid) + nh * Dh + ((uint32_t)n - nh) * Dm;
       const uint32_t hyp = n > 0 ? (uint32_t)((hm >> (n - 1)) & 1ull) : lget(gs.hyp, gid);
-      bool st = i >= (int)kp.ns_aa;
-      if ((uint32_t)i % kp.samples_per_batch == 0) {  // ADAPTIVE == 1 (:147-158)
+      bool st = i >= (int)kp->ns_aa;
+      if ((uint32_t)i % kp->samples_per_batch == 0) {  // ADAPTIVE == 1 (:147-158)
         const double avg = s1 / i, sd = sqrt((s2 - avg * s1) / (i - 1));
-        if (1.96 * sd / sqrt((double)i) <= (double)kp.max_tolerance * avg) st = true;
+        if (1.96 * sd / sqrt((double)i) <= (double)kp->max_tolerance * avg) st = true;
       }
       if (st) stop = 1;
-      else if (kp.cont && (uint32_t)((int)kp.ns_aa - i) >= kp.cont_min_left &&
-               cont_push(kp, lget(gs.px, gid), lget(gs.py, gid), lget(gs.slot, gid), (uint32_t)i, O, ret, s1, s2))
+      else if (kp->cont && (uint32_t)((int)kp->ns_aa - i) >= kp->cont_min_left &&
+               cont_push(*kp, lget(gs.px, gid), lget(gs.py, gid), lget(gs.slot, gid), (uint32_t)i, O, ret, s1, s2))
         stop = 2;  // handed over: the heavy block writes the result
       if (stop == 1) {
         const uint32_t slot = lget(gs.slot, gid);
@@ -1071,9 +1090,9 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
         }
 #endif
         const spec r = ret / (float)i;
-        kp.rgb[3 * slot] = r.r; kp.rgb[3 * slot + 1] = r.g; kp.rgb[3 * slot + 2] = r.b;
-        kp.count[slot] = i;
-        if (kp.draws) kp.draws[slot] = O;
+        kp->rgb[3 * slot] = r.r; kp->rgb[3 * slot + 1] = r.g; kp->rgb[3 * slot + 2] = r.b;
+        kp->count[slot] = i;
+        if (kp->draws) kp->draws[slot] = O;
       } else if (stop == 0) {
         lput(gs.rr, gid, ret.r); lput(gs.rg, gid, ret.g); lput(gs.rb, gid, ret.b);
         lput(gs.s1, gid, s1); lput(gs.s2, gid, s2);
@@ -1084,7 +1103,7 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
     if (stop) have = false;
     RRT_ACC(t_fold, tf0);
   }
-  cont_wave_done(kp, lane);
+  cont_wave_done(*kp, lane);
 #if RRT_PROFILE
   if (wd && lane == 0) wd[3] = 0xdeadu;  // exited
 #endif

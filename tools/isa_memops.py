@@ -10,6 +10,12 @@ kernel and per out-of-line device function, the counts of
 
 and the instruction total.  It counts these instruction classes and nothing else.
 
+With --loops it prints instead, per kernel and function, the loops that contain no inner loop
+(found from the listing's backward branches: a label and the last branch back to it), each with its
+instruction count, FP64 and other VALU instructions, v_readlane / v_writelane, scalar loads, scratch
+loads and stores, global and LDS accesses: where a kernel short of VALU issue slots spends them, and
+which of them move spilled SGPRs (launch constants by stage).  All counts are static.
+
 A flat access needs a 64-bit VGPR address, counts on both wait counters and may return out of
 order; an access whose address space the source states is a ds_*, global_* or s_load instruction
 (address spaces).  With --check, the exit status is 1 if a flat memory instruction
@@ -81,6 +87,108 @@ def functions(path):
     return {n: (c, cl, n in kernels) for n, (c, cl) in out.items()}
 
 
+LOOP_COLS = ["insts", "fp64", "valu", "rdlane", "wrlane", "s_ld", "scr_ld", "scr_st", "glob", "lds"]
+
+
+def loop_class(op):
+    """the --loops column of one instruction, or None (it still counts in insts)"""
+    if re.match(r"v_readlane_b32", op):
+        return "rdlane"
+    if re.match(r"v_writelane_b32", op):
+        return "wrlane"
+    if op.startswith("v_"):
+        return "fp64" if re.search(r"_f64(?:_|$)", op) else "valu"
+    if re.match(r"s_(?:buffer_)?load_", op):
+        return "s_ld"
+    if op.startswith("scratch_load_"):
+        return "scr_ld"
+    if op.startswith("scratch_store_"):
+        return "scr_st"
+    if re.match(r"global_(?:load|store|atomic)_", op):
+        return "glob"
+    if op.startswith("ds_"):
+        return "lds"
+    return None
+
+
+def innermost_loops(path):
+    """name -> [(header label, first line, last line, counts)] of the loops without an inner loop.
+
+    A loop is a label and the last branch back to it from further down the same function (the
+    listing's backward branches); it is innermost if no other loop lies within its span."""
+    out = {}
+    name, ins, labels = None, [], {}
+
+    def close():
+        if name is None:
+            return
+        span = {}  # header index -> last back-branch index
+        for i, (_ln, op, ops) in enumerate(ins):
+            if not re.match(r"s_c?branch", op):
+                continue
+            tgt = ops.split(",")[-1].strip()
+            if tgt in labels and labels[tgt] <= i:
+                h = labels[tgt]
+                span[h] = max(span.get(h, i), i)
+        res = []
+        for h, e in sorted(span.items()):
+            if any((h2, e2) != (h, e) and h <= h2 and e2 <= e for h2, e2 in span.items()):
+                continue
+            cnt = dict.fromkeys(LOOP_COLS, 0)
+            for _ln, op, _ops in ins[h : e + 1]:
+                cnt["insts"] += 1
+                c = loop_class(op)
+                if c:
+                    cnt[c] += 1
+            label = next(l for l, k in labels.items() if k == h)
+            res.append((label, ins[h][0], ins[e][0], cnt))
+        out[name] = res
+
+    for ln, line in enumerate(open(path), 1):
+        m = re.match(r"^(_Z\w+|[A-Za-z_]\w*):\s*(?:;.*)?$", line)
+        if m and not line.startswith(".L"):
+            close()
+            name, ins, labels = m.group(1), [], {}
+            continue
+        if re.match(r"^\.Lfunc_end\d+:", line):
+            close()
+            name = None
+            continue
+        if name is None:
+            continue
+        m = re.match(r"^(\.L\w+):", line)
+        if m:
+            labels.setdefault(m.group(1), len(ins))  # the next instruction's index
+            continue
+        if not line.startswith("\t"):
+            continue
+        s = line.strip()
+        if not s or s[0] in ";.":
+            continue
+        op, _, ops = s.partition(" ")
+        ins.append((ln, op, ops.split(";")[0]))
+    close()
+    return out
+
+
+def print_loops(paths, only):
+    for path in paths:
+        kernels = {n for n, (_c, _cl, k) in functions(path).items() if k}
+        print(f"# {path.split('/')[-1]}: loops without an inner loop (label, listing lines)")
+        for n, loops in innermost_loops(path).items():
+            tag = ("K " if n in kernels else "f ") + short(n)
+            if not loops or (only and only not in tag):
+                continue
+            print(tag)
+            print(f"  {'loop':12s} {'lines':>15s} " + " ".join(f"{c:>6s}" for c in LOOP_COLS))
+            tot = dict.fromkeys(LOOP_COLS, 0)
+            for label, a, b, cnt in loops:
+                print(f"  {label:12s} {f'{a}-{b}':>15s} " + " ".join(f"{cnt[c]:6d}" for c in LOOP_COLS))
+                for c in LOOP_COLS:
+                    tot[c] += cnt[c]
+            print(f"  {'total':12s} {len(loops):>9d} loops " + " ".join(f"{tot[c]:6d}" for c in LOOP_COLS))
+
+
 def short(name):
     """the mangled name's readable core: function name + its template arguments' literals"""
     core = name
@@ -103,7 +211,14 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("listings", nargs="+")
     ap.add_argument("--check", action="store_true", help="fail on a flat memory instruction in the depth <= 1 kernels")
+    ap.add_argument("--loops", action="store_true",
+                    help="per kernel and function, the loops without an inner loop: instructions, FP64, other VALU, "
+                         "lane moves, scalar / scratch / global / LDS accesses")
+    ap.add_argument("--only", default="", help="with --loops: only functions whose printed name contains this")
     a = ap.parse_args()
+    if a.loops:
+        print_loops(a.listings, a.only)
+        return
     bad = []
     for path in a.listings:
         fns = functions(path)
