@@ -485,6 +485,13 @@ typedef struct {
                                   between adaptive steps (continuations) */
 } rrt_stats;
 int rrt_get_stats(const rrt_ctx* ctx, rrt_stats* out);
+/* Diagnostics, host only: the camera miss proof gate's constant a launch planned now would carry
+ * (DESIGN.md §5 "Proof gate"), from RRT_AB_PROVE_FIRST in the environment, which every launch reads anew.
+ * 0 (the default, also for text that is no number): the area- and point-light batch kernels run the per-ray
+ * miss proof only in front of rays expected to miss; 1 (any other number): in front of every ray, as before
+ * the gate.  Results are the same at either value.  For diagnostics and tests only: unstable, it may change
+ * or go with the A/B knob it reports, without a new RRT_ABI_VERSION. */
+uint32_t rrt_plan_prove_first(void);
 /* Diagnostics: evaluate the device's restatement of the host C library's transcendentals
  * (csrc/rrt_glibm.h -- the reference's sin/cos (sampler.cpp:53-55, environment_light.cpp:97-137),
  * acos (sampler.cpp:20, bsdf.h:166, environment_light.cpp:88), atan2 (environment_light.cpp:89),

@@ -386,7 +386,9 @@ struct KParams {
   // batch kernel: a wave whose oldest pixel has run this long (wall-clock ticks, 100 MHz) takes
   // issue priority 2, four times as long priority 3 (rrt_sample.hip tail_prio)
   uint32_t prio_ticks;
-  uint32_t prio_pad;
+  // camera miss proof gate: 1: the LEAN batch kernels prove every slot's ray before its
+  // exact march (A/B, the behaviour before the gate); 0: only the slots expected to miss
+  uint32_t prove_first;
   DKerrProof kproof;      // Kerr builds: the shadow rays' occlusion proof (kp.occ's face triangles)
   // the pixel pass's first level (rrt_strip_proof_kernel): strips of 64 consecutive claim indices
   // proven as wholes -- flag 1 per strip -- before the per-pixel level (null: per-pixel pass only)

@@ -882,7 +882,10 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
       if (m0 < RRT_SLOTS) my = m0;
     }
     // the camera query of slot sl (Camera::generate_ray, part1_code.cpp:182-187, at its jitter)
-    auto slot_query = [&](uint32_t sl, Isect* is) -> bool {
+    // prove: run the miss proof in front of the exact march.  It pays only where the ray is expected
+    // to miss: a ray that enters the root box cannot be proven, and its proof runs up to the entry
+    // row before the march starts again from row 0 (DESIGN.md §5 "Proof gate").
+    auto slot_query = [&](uint32_t sl, Isect* is, bool prove) -> bool {
       const DCamera& cam = kp->cam;
       Rng g; g.key = lget(gs.key, gid); g.ctr = O0 + sl * Dm;
       double jx, jy; g.grid(jx, jy);
@@ -892,7 +895,7 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
       const v3 w = (smul(vx, ld3(cam.c2w0)) + smul(vy, ld3(cam.c2w1))) + smul(-1.0, ld3(cam.c2w2));
       const v3 wd = unit(w);
       // (the miss proof's constants are live inside it only; query renews its own)
-      if (camera_proven_miss<false, LEAN == V_KERR>(kp_stage<SC>(*kp), ld3(cam.pos), wd, cn)) return false;
+      if (prove && camera_proven_miss<false, LEAN == V_KERR>(kp_stage<SC>(*kp), ld3(cam.pos), wd, cn)) return false;
       return query_nx<false, false, LEAN == V_KERR, 0, is_lean(LEAN), SC>(*kp, ld3(cam.pos), wd, is, cn);
     };
     const uint64_t gmask = (G >= 64 ? ~0ull : ((1ull << G) - 1ull)) << gbase;  // this group's lanes
@@ -902,12 +905,51 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
     bool hk = false;
     int n_step = 0;             // samples the step resolves
     bool resolved = !have;      // (group-uniform)
+    // the outcome the round's slots are expected to have (group-uniform): the pixel's hypothesis,
+    // then each chain round's guess.  The LEAN builds prove only the slots expected to miss
+    // (A/B: kp->prove_first proves every slot first, as the general build does).
+    bool expect_hit = lget(gs.hyp, gid) != 0;
+    // Move each hit sample's record into its own lane's ShadeLds slot: every move is read before any
+    // is written, so a lane may give its slot away and receive another.  A record that was given up
+    // (state 3) is computed again from the same ray, the same hit: here (requery, the general and
+    // Kerr builds), or -- the LEAN builds -- by one more round of the loop below on the returned
+    // slot, so that the kernel holds no further copy of the query; no proof can succeed there.
+    auto move_records = [&](bool requery) -> uint32_t {
+      const bool hit = have && (int)gl < n_step && hk;
+      const bool lost = hit && lget(&gs.sst[gid][0], mk) == 3;
+      const uint32_t src = (t - gl) + lget(&gs.sown[gid][0], mk);
+      const bool move = hit && !lost && src != t;
+      Isect is0 = {};
+      if (move) {
+        is0.hit_p = V(lget(cl.hp[0], src), lget(cl.hp[1], src), lget(cl.hp[2], src));
+        is0.n = V(lget(cl.nn[0], src), lget(cl.nn[1], src), lget(cl.nn[2], src));
+        is0.w_out = V(lget(cl.wo[0], src), lget(cl.wo[1], src), lget(cl.wo[2], src));
+        is0.bsdf = (int)lget(cl.bsdf, src);
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      if (requery && lost) slot_query(mk, &is0, true);
+      if (move || (requery && lost)) park_hit(cl, t, is0);
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      return lost ? mk : RRT_SLOTS;
+    };
+    bool fin = false;  // the LEAN builds' last round: the given-up records, after the moves
     for (int round = 0;; ++round) {
-      const bool need = my < RRT_SLOTS;
+      bool need = my < RRT_SLOTS;
 #if RRT_PROFILE
       if (wd && lane == 0) { wd[1] = (have ? 1u : 0u) | (done ? 2u : 0u) | ((uint32_t)round << 8); wd[2] = lget(gs.slot, gid); wd[3] = 0x22u; }
 #endif
-      if (__ballot(need) == 0) break;
+      if (__ballot(need) == 0) {
+        if (!SC || fin) break;
+        fin = true;
+        stage();
+        my = move_records(false);
+        need = my < RRT_SLOTS;
+        if (__ballot(need) == 0) break;
+      }
       if (round > 0) tail_prio();
       stage();
 #if RRT_PROFILE
@@ -917,7 +959,7 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
       bool h = false;
       if (need) {
         Isect is;
-        h = slot_query(my, &is);
+        h = slot_query(my, &is, !SC || (!fin && (!expect_hit || kp->prove_first)));
         if (h) park_hit(cl, t, is);  // nothing of the hit stays live across later rounds
         held = my;
         lput(&gs.sst[gid][0], my, (uint8_t)(h ? 2 : 1));
@@ -937,6 +979,7 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       my = RRT_SLOTS;
+      if (fin) break;
       if (resolved) continue;
       RRT_T0(tw0);
       // walk the chain over the known slots (group-uniform)
@@ -964,8 +1007,9 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
       const bool free_b = open && !on_chain && !free_a;
       const uint64_t ba = __ballot(free_a), bb = __ballot(free_b);
       const uint32_t rank = free_a ? (uint32_t)__popcll(ba & lt) : (uint32_t)(__popcll(ba & gmask) + __popcll(bb & lt));
+      expect_hit = k > 0 ? 2 * kh >= k : lget(gs.hyp, gid) != 0;
       if (free_a || free_b) {
-        const uint32_t guess = (k > 0 ? 2 * kh >= k : lget(gs.hyp, gid) != 0) ? S1 : 1u;
+        const uint32_t guess = expect_hit ? S1 : 1u;
         uint32_t mm = m, j = 0;
         for (int kk = k; kk < left && mm < RRT_SLOTS; ++kk) {
           const uint32_t st = lget(&gs.sst[gid][0], mm);
@@ -985,26 +1029,9 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
     const bool act = have && (int)gl < n_step;
     const bool hit = act && hk;
     const uint32_t off = O0 + mk * Dm;
-    stage();  // `lost` re-query
-    {  // move each hit sample's record into its own lane's ShadeLds slot (recompute a given-up one)
-      const bool lost = hit && lget(&gs.sst[gid][0], mk) == 3;
-      const uint32_t src = (t - gl) + lget(&gs.sown[gid][0], mk);
-      const bool move = hit && !lost && src != t;
-      Isect is0 = {};
-      if (move) {
-        is0.hit_p = V(lget(cl.hp[0], src), lget(cl.hp[1], src), lget(cl.hp[2], src));
-        is0.n = V(lget(cl.nn[0], src), lget(cl.nn[1], src), lget(cl.nn[2], src));
-        is0.w_out = V(lget(cl.wo[0], src), lget(cl.wo[1], src), lget(cl.wo[2], src));
-        is0.bsdf = (int)lget(cl.bsdf, src);
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      if (lost) slot_query(mk, &is0);  // the same ray: the same hit
-      if (move || lost) park_hit(cl, t, is0);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if constexpr (!SC) {
+      stage();  // `lost` re-query
+      move_records(true);
     }
     const uint64_t hits = __ballot(hit);
 

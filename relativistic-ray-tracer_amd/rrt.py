@@ -150,7 +150,8 @@ EXPORTS = ["rrt_abi_version", "rrt_create", "rrt_destroy", "rrt_last_error", "rr
            "rrt_get_occluders", "rrt_group_create", "rrt_group_render", "rrt_group_destroy", "rrt_libm_eval",
            "rrt_set_proof_audit", "rrt_get_proof_audit", "rrt_get_search_tree4", "rrt_trace_rays",
            "rrt_trace_rays_device", "rrt_trace_camera", "rrt_trace_camera_device", "rrt_env_eval", "rrt_set_disk",
-           "rrt_get_disk", "rrt_disk_eval", "rrt_blackbody_tint", "rrt_disk_sample"]
+           "rrt_get_disk", "rrt_disk_eval", "rrt_blackbody_tint", "rrt_disk_sample",
+           "rrt_plan_prove_first"]
 AUDIT_KINDS = ("camera", "shadow", "pixel", "strip", "kerr", "zero")  # include/rrt.h RRT_AUDIT_*
 
 _lib = None
@@ -198,6 +199,9 @@ def lib():
         if hasattr(L, "rrt_region_tiles"):  # absent from older builds loaded through RRT_LIB
             L.rrt_region_tiles.argtypes = [C.c_uint32] * 7 + [vp, C.c_uint32]
         L.rrt_get_stats.argtypes = [vp, C.POINTER(Stats)]
+        if hasattr(L, "rrt_plan_prove_first"):  # absent from older builds loaded through RRT_LIB
+            L.rrt_plan_prove_first.argtypes = []
+            L.rrt_plan_prove_first.restype = C.c_uint32
         L.rrt_get_launch_times.argtypes = [vp, C.c_uint32, vp, vp]
         L.rrt_libm_eval.argtypes = [vp, C.c_int, vp, vp, vp, C.c_uint64]
         if hasattr(L, "rrt_env_eval"):  # absent from older builds loaded through RRT_LIB
