@@ -1834,6 +1834,33 @@ __device__ __forceinline__ bool rect_miss_proof(const KParams& kp, double px, do
       const double D = w * w + wp * wp - 2.0 * mp.co1 * fabs(wp) * w;
       far = far && si2 > rb * rb * D;
     }
+    // Separating half-space: in a ray's own plane (coordinates about the hole on X and
+    // its axis Y) the segment runs from a eA to b eB, eA = sg (ea, eb) and eB = sign(v) (na, nb) the
+    // same for every ray of the rectangle (one sign history), a in [rho / (|vp| + dvp), rp] and b in
+    // [rho / (av + dv), r].  With n the central segment's in-plane unit normal, n . eA > 0 and
+    // n . eB > 0, every point of every such segment has n-coordinate >= dmin (a convex combination of
+    // its ends).  In space n3 = n_x X + n_y Yc: a point alpha X + beta Y has n3 . (P - c) = alpha n_x +
+    // beta n_y (Y . Yc) >= alpha n_x + beta n_y - |beta| dY^2 / 2, |beta| at most at an end.  The
+    // box's support about the hole in direction n3 is hs, the widening by m0 on every axis adds at
+    // most sqrt(3) m0 to it: a row with dmin beyond both is clear of the widened box.  Rows j >= 1;
+    // anything else (NaN included) falls through to the slab test.
+    if (!far && kp.halfspace && j >= 1) {
+      const double sv = v[1] < 0.0 ? -1.0 : 1.0, avp = fabs(vp[1]);
+      const double eax = sg * ea, eay = sg * eb, ebx = sv * na, eby = sv * nb;
+      const double ac = mp.rho / avp, bc = mp.rho / av;
+      const double tx = bc * ebx - ac * eax, ty = bc * eby - ac * eay;
+      const double it = 1.0 / sqrt(tx * tx + ty * ty);
+      double nx = -ty * it, ny = tx * it, gA = nx * eax + ny * eay;
+      if (gA < 0.0) { nx = -nx; ny = -ny; gA = -gA; }
+      const double gB = nx * ebx + ny * eby;
+      const double dmin = fmin(mp.rho / (avp + dvp) * gA, mp.rho / (av + dv) * gB);
+      const double bmax = fmax(rp * fabs(eb), r * fabs(nb));
+      const v3 n3 = smul(nx, X) + smul(ny, Yc);
+      const double hs = fmax(n3.x * (mp.lo[0] - c.x), n3.x * (mp.hi[0] - c.x)) +
+                        fmax(n3.y * (mp.lo[1] - c.y), n3.y * (mp.hi[1] - c.y)) +
+                        fmax(n3.z * (mp.lo[2] - c.z), n3.z * (mp.hi[2] - c.z));
+      far = gA > 0.0 && gB > 0.0 && dmin * (1.0 - 1e-6) - bmax * (0.5 * dY * dY) > hs + 3.0 * m0;
+    }
     if (!far) {
       const double ia = mp.rho / vp[1], ib = mp.rho / v[1];
       const v3 pa = j == 0 ? O : V(c.x + (ea * ia) * X.x + (eb * ia) * Yc.x, c.y + (ea * ia) * X.y + (eb * ia) * Yc.y,

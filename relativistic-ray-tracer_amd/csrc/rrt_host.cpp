@@ -1727,17 +1727,23 @@ struct AbKnobs {
   uint32_t heavy_g;   // 28..31: heavy waves per CU (default 2)
   const char *cont, *cont_min, *cont_room, *cont_waiters, *prio_ticks;  // RRT_AB_CONT .. RRT_AB_PRIO_TICKS
   const char* prove_first;  // RRT_AB_PROVE_FIRST
+  const char* no_halfspace;  // RRT_AB_NO_HALFSPACE
   static uint32_t u32(const char* s, uint32_t dflt) { return s ? (uint32_t)std::strtoul(s, nullptr, 10) : dflt; }
 };
 // The camera miss proof gate's launch constant (KParams::prove_first): 0, the default: the LEAN
 // batch kernels prove only the slots expected to miss; A/B: RRT_AB_PROVE_FIRST=1 (any non-zero number): they
 // prove every slot first, the behaviour before the gate.
 static uint32_t plan_prove_first(const AbKnobs& ab) { return AbKnobs::u32(ab.prove_first, 0u) ? 1u : 0u; }
+// The pixel pass's half-space rule (KParams::halfspace): 1, the default: rect_miss_proof tries it
+// before the widened slab test; A/B: RRT_AB_NO_HALFSPACE=1 (any non-zero number): the slab test alone.  The
+// frames are the same bits either way: the rule only moves pixels from the batch kernel to the pass.
+static uint32_t plan_halfspace(const AbKnobs& ab) { return AbKnobs::u32(ab.no_halfspace, 0u) ? 0u : 1u; }
 static AbKnobs read_ab_knobs(uint32_t v) {
   return AbKnobs{v & 0xffu, (v >> 8) & 0xfu, (v >> 12) & 0xfu, (v >> 16) & 0xfu, (v >> 20) & 3u, ((v >> 22) & 1u) != 0,
                  ((v >> 23) & 1u) != 0, (v >> 24) & 0xfu, (v >> 28) & 0xfu, std::getenv("RRT_AB_CONT"),
                  std::getenv("RRT_AB_CONT_MIN"), std::getenv("RRT_AB_CONT_ROOM"), std::getenv("RRT_AB_CONT_WAITERS"),
-                 std::getenv("RRT_AB_PRIO_TICKS"), std::getenv("RRT_AB_PROVE_FIRST")};
+                 std::getenv("RRT_AB_PRIO_TICKS"), std::getenv("RRT_AB_PROVE_FIRST"),
+                 std::getenv("RRT_AB_NO_HALFSPACE")};
 }
 
 // the RNG draws of one camera sample that hits, at depth <= 1: jitter + the direct-lighting samplers
@@ -1945,6 +1951,7 @@ static LaunchPlan plan_launch(const rrt_ctx* c, const rrt_render_params* p, cons
   // tail priority threshold (A/B: RRT_AB_PRIO_TICKS in the environment)
   kp.prio_ticks = AbKnobs::u32(ab.prio_ticks, 50000u);
   kp.prove_first = plan_prove_first(ab);
+  kp.halfspace = plan_halfspace(ab);
   kp.n_pixels = pl.n_pixels;
   kp.n_queues = batch ? pl.n_queues : 0u;
   kp.q_stripe = pl.stripe ? 1u : 0u;
@@ -2500,7 +2507,6 @@ extern "C" int rrt_render(rrt_ctx* c, const rrt_render_params* p, uint32_t x0, u
 
 // (the knobs as plan_launch reads them, so the value is the one its KParams would carry)
 extern "C" uint32_t rrt_plan_prove_first(void) { return plan_prove_first(read_ab_knobs(0u)); }
-
 extern "C" int rrt_get_stats(const rrt_ctx* cc, rrt_stats* out) {
   rrt_ctx* c = const_cast<rrt_ctx*>(cc);
   if (!c || !out) return RRT_E_INVALID;

@@ -397,7 +397,10 @@ struct KParams {
   // 2^audit_shift-th proven ray (and pixel) against the exact march; tallies [2 k] checked,
   // [2 k + 1] violations per proof k (RRT_AUDIT_*); null: no audit
   RRT_GLOBAL_AS unsigned long long* audit;  // 64-bit: a 1080p frame audited at every_log2 = 0 exceeds 2^32 checks
-  uint32_t audit_shift, audit_pad;
+  uint32_t audit_shift;
+  // pixel pass (rrt_device.h rect_miss_proof): 1: a row near the root box tries the
+  // separating half-space rule before the widened slab test; 0 (A/B): the slab test alone
+  uint32_t halfspace;
   // continuations: a batch-kernel group whose pixel still has >= cont_min_left
   // samples to go after an adaptive check hands it to a heavy block that is waiting for work
   // (cont_ctl[RRT_CONT_IDLE] > 0), which renders the remaining steps' draw-offset slots in parallel.

@@ -1,0 +1,130 @@
+"""numpy mirror of the pixel pass's proof (relativistic-ray-tracer_amd/csrc/rrt_device.h
+rect_miss_proof) with its separating half-space rule, one rectangle at a time, given the
+rectangle's centre and corner ray directions.
+
+TEST INFRASTRUCTURE ONLY (tests/test_halfspace_proof.py, tools/strip_proof_sweep.py --mirror rect):
+the product runs the HIP version.
+
+prove(..., halfspace=False) is tests/pixel_proof_sim.py prove, statement for statement.  With
+halfspace=True a row (j >= 1) whose four-corner line test fails first tries the rule of DESIGN.md §5
+"Separating half-space": in a ray's own plane about the hole its segment runs from a eA to b eB,
+the unit vectors eA and eB the same for every ray of the rectangle and a, b in intervals the
+recurrences give; with n the central segment's unit normal, n . eA > 0 and n . eB > 0, every point
+of every such segment lies at least dmin along n, a plane turned by at most dY from the central one
+costs |beta| dY^2 / 2 of that, and the root box widened by the camera proof's margin reaches no
+farther along n3 = n_x X + n_y Yc than its support plus sqrt(3) times the margin.  A row that
+fails the rule takes the widened slab test as before, so the rule only adds proven rectangles.
+"""
+import numpy as np
+
+from miss_proof_sim import ETA, KAPPA, seg_clear
+
+
+def halfspace_clear(K, X, Yc, dY, rho, ea, eb, na, nb, vpc, vc, dvp, dv, rp, r, m0):
+    """The rule at one row: central (v_prev, v) = (vpc, vc), spreads (dvp, dv), the frames (ea, eb)
+    of A and (na, nb) of B, rp and r the upper bounds on |A - c| and |B - c|."""
+    c, lo, hi = K["c"], K["lo"], K["hi"]
+    sg = -1.0 if vpc < 0.0 else 1.0
+    sv = -1.0 if vc < 0.0 else 1.0
+    av, avp = abs(vc), abs(vpc)
+    eax, eay, ebx, eby = sg * ea, sg * eb, sv * na, sv * nb
+    ac, bc = rho / avp, rho / av
+    tx, ty = bc * ebx - ac * eax, bc * eby - ac * eay
+    with np.errstate(all="ignore"):
+        it = 1.0 / np.sqrt(tx * tx + ty * ty)
+        nx, ny = -ty * it, tx * it
+        gA = nx * eax + ny * eay
+        if gA < 0.0:
+            nx, ny, gA = -nx, -ny, -gA
+        gB = nx * ebx + ny * eby
+        dmin = min(rho / (avp + dvp) * gA, rho / (av + dv) * gB)
+        bmax = max(rp * abs(eb), r * abs(nb))
+        n3 = nx * X + ny * Yc
+        hs = float(np.maximum(n3 * (lo - c), n3 * (hi - c)).sum())
+        return bool(gA > 0.0 and gB > 0.0 and dmin * (1.0 - 1e-6) - bmax * (0.5 * dY * dY) > hs + 3.0 * m0)
+
+
+def prove(K, O, dc, corners, halfspace=True, stats=None):
+    """True if every ray through the rectangle (centre direction dc, corner directions corners
+    [4,3]) is a proven miss.  stats (a dict, optional): counts the rows the rule cleared."""
+    c = K["c"]
+    x0 = O - c
+    r0 = np.sqrt(x0 @ x0)
+    u0 = 1.0 / r0
+    X = x0 * u0
+    dxc = dc @ X
+    Yc = dc - dxc * X
+    dyc = np.sqrt(Yc @ Yc)
+    if not dyc > 1e-3:
+        return False
+    Yc = Yc / dyc
+    dlo = dhi = dxc
+    dY = dd = 0.0
+    dymin = dyc
+    for d in corners:
+        dx = d @ X
+        dlo, dhi = min(dlo, dx), max(dhi, dx)
+        yv = d - dx * X
+        dy = np.sqrt(yv @ yv)
+        if not dy > 1e-3:
+            return False
+        dymin = min(dymin, dy)
+        dY = max(dY, np.linalg.norm(yv / dy - Yc))
+        dd = max(dd, np.linalg.norm(d - dc))
+    if not dd <= 0.25 * dymin:  # +-X (where y turns round) kept well outside the rectangle
+        return False
+    slack = 2.0 * dd * dd + 1e-12
+    wdx = dhi - dlo
+    dlo -= 0.05 * wdx + slack
+    dhi += 0.05 * wdx + slack
+    dY = 1.25 * dY + slack
+    if not (dlo > -1.0 and dhi < 1.0):
+        return False
+    dxs = np.array([dlo, dxc, dhi])
+    up0 = -u0 * dxs / np.sqrt(1.0 - dxs * dxs)
+    vp = np.full(3, K["rho"] * u0)
+    s = u0 * K["co1"] - up0 * K["si"] / K["rho"]
+    ea, eb, sig, rp, dpa, dvp = 1.0, 0.0, 1.0, r0, 0.0, 0.0
+    si2 = K["si"] * K["si"]
+    rho = K["rho"]
+    for j in range(K["steps"]):
+        up = (vp * K["co1"] - rho * s) / K["si"]
+        s = np.abs(vp) / rho
+        f1 = -s + K["k15"] * s * s
+        u2 = s + up * (K["dt"] * 0.5)
+        f2 = -u2 + K["k15"] * u2 * u2
+        u3 = u2 + f1 * (K["dt"] * K["dt"] / 4.0)
+        f3 = -u3 + K["k15"] * u3 * u3
+        v = s + up * K["dt"] + (f1 + f2 + f3) * (K["dt"] * K["dt"] / 6.0)
+        ok = bool(np.all(np.abs(v) >= KAPPA * (s + np.abs(up) * K["dt"])))
+        dv = 1.5 * max(abs(v[0] - v[1]), abs(v[2] - v[1]))
+        av = abs(v[1])
+        if not (ok and (v[0] < 0) == (v[1] < 0) and (v[2] < 0) == (v[1] < 0) and av > 2.0 * dv):
+            return False
+        sg = -1.0 if vp[1] < 0.0 else 1.0
+        a, b = sg * K["co1"], sig * K["si1"]
+        na, nb = a * ea - b * eb, a * eb + b * ea
+        sig *= sg
+        r = rho / (av - dv) * (1.0 + 1e-6)
+        dpb = rho * dv / (av * (av - dv)) * (1.0 + 1e-6) + r * abs(nb) * dY
+        m0 = ETA * (max(rp, r) + K["scale"])
+        m = m0 + max(dpa, dpb)
+        rb = K["r_ball"] + m0
+        far = True
+        for k in range(4):
+            w = v[1] + (dv if k & 1 else -dv)
+            wp = vp[1] + (dvp if k & 2 else -dvp)
+            D = w * w + wp * wp - 2.0 * K["co1"] * abs(wp) * w
+            far = far and si2 > rb * rb * D  # the line distance, a lower bound on the segment's
+        if not far and halfspace and j >= 1:
+            far = halfspace_clear(K, X, Yc, dY, rho, ea, eb, na, nb, vp[1], v[1], dvp, dv, rp, r, m0)
+            if far and stats is not None:
+                stats["rows"] = stats.get("rows", 0) + 1
+        if not far:
+            pa = O if j == 0 else c + (ea * rho / vp[1]) * X + (eb * rho / vp[1]) * Yc
+            pb = c + (na * rho / v[1]) * X + (nb * rho / v[1]) * Yc
+            if not seg_clear(pa[None], pb[None], K["lo"], K["hi"], np.array([m]))[0]:
+                return False
+        vp = v
+        rp, dpa, dvp, ea, eb = r, dpb, dv, na, nb
+    return True

@@ -6,7 +6,8 @@ every proven strip -- its four corners and two random jitters -- is marched by t
 (a violation otherwise).  Usage: python3 tools/strip_proof_sweep.py --case cfg3_bunny_1080p_s64 --strips 2000
 --fov H: the case's camera with a horizontal field of view of H degrees (vertical from the frame's
 aspect), to sweep wide-angle framings; small frames (e.g. --case spheres_96x72_s8) make strips that
-subtend large angles."""
+subtend large angles.
+--mirror rect: the mirror with the separating half-space rule (tests/rect_proof_sim.py)."""
 import argparse
 import ctypes as C
 import json
@@ -22,7 +23,8 @@ import oracle_lib as O  # noqa: E402
 import rrt  # noqa: E402
 from golden_cases import Case  # noqa: E402
 from miss_proof_sim import constants  # noqa: E402
-from pixel_proof_sim import prove  # noqa: E402
+import pixel_proof_sim  # noqa: E402
+import rect_proof_sim  # noqa: E402
 from test_pixel_proof import _loose_root_hit  # noqa: E402
 
 
@@ -33,7 +35,10 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--out", default=None)
     ap.add_argument("--fov", type=float, default=None, help="override hFov (degrees)")
+    ap.add_argument("--mirror", choices=["pixel", "rect"], default="pixel",
+                    help="pixel: tests/pixel_proof_sim.py; rect: tests/rect_proof_sim.py (with the half-space rule)")
     a = ap.parse_args()
+    prove = rect_proof_sim.prove if a.mirror == "rect" else pixel_proof_sim.prove
     c = Case(a.case)
     bh = np.array(c.cfg["bh"], np.float64)
     r = rrt.Renderer(device=-1)
@@ -76,7 +81,7 @@ def main():
                     k = O.lib().ro_micro_chain(bh, o2, d2, out, K["steps"] + 1)
                     rays += 1
                     viol += int(_loose_root_hit(lo, hi, out[:k]).any())
-    rec = dict(case=a.case, hfov=hfov, strips=a.strips, proven=proven, rays_checked=rays, violations=viol)
+    rec = dict(case=a.case, mirror=a.mirror, hfov=hfov, strips=a.strips, proven=proven, rays_checked=rays, violations=viol)
     print(json.dumps(rec))
     if a.out:
         json.dump(rec, open(a.out, "w"), indent=1)
