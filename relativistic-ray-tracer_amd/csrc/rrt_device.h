@@ -1715,6 +1715,104 @@ __device__ __forceinline__ bool camera_proven_miss(const KParams& kp, v3 o, v3 d
   return r;
 }
 
+// ------------------------------------------------------------------ per-sample rules
+// The rules of PathTracer::raytrace_pixel (part1_code.cpp:125-163) and of the claim order that every
+// render kernel shares: one statement per rule, and a kernel calls it.  All of them
+// inline; `kp` is the caller's view of the launch constants at that point (a LEAN build's stage).
+
+// The wave's lanes hand values to each other through LDS: writes before it, reads after it
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Camera::generate_ray (part1_code.cpp:182-187) at raster position (sx, sy): the point of the sensor
+// plane (the thin lens of camera.cpp:176-184 starts from it too) ...
+__device__ __forceinline__ void sensor_point(const KParams& kp, double sx, double sy, double& vx, double& vy) {
+  const DCamera& cam = kp.cam;
+  const double cx = sx / kp.frame_w, cy = sy / kp.frame_h;
+  vx = (1 - cx) * cam.blx + cx * -cam.blx; vy = (1 - cy) * cam.bly + cy * -cam.bly;
+}
+// ... and the pinhole ray's direction through it
+__device__ __forceinline__ v3 pixel_ray_dir(const KParams& kp, double sx, double sy) {
+  const DCamera& cam = kp.cam;
+  double vx, vy;
+  sensor_point(kp, sx, sy, vx, vy);
+  const v3 w = (smul(vx, ld3(cam.c2w0)) + smul(vy, ld3(cam.c2w1))) + smul(-1.0, ld3(cam.c2w2));
+  return unit(w);
+}
+// A sample's raster position (:132-136): the pixel's centre with one sample, else the grid sampler's jitter
+__device__ __forceinline__ void sample_pos(const KParams& kp, Rng& g, uint32_t x, uint32_t y, double& sx, double& sy) {
+  sx = (double)x; sy = (double)y;
+  if (kp.ns_aa == 1) { sx += 0.5; sy += 0.5; }
+  else { double jx, jy; g.grid(jx, jy); sx += jx; sy += jy; }
+}
+// The adaptive stop (ADAPTIVE == 1, :147-158) after n samples whose illuminances sum to s1 and their
+// squares to s2; the caller tests it where n % samples_per_batch == 0.  N: int or uint32_t, as the
+// caller counts
+template <class N>
+__device__ __forceinline__ bool adaptive_stop(const KParams& kp, double s1, double s2, N n) {
+  const double avg = s1 / n, sd = sqrt((s2 - avg * s1) / (n - 1));
+  return 1.96 * sd / sqrt((double)n) <= (double)kp.max_tolerance * avg;
+}
+
+// A pixel by its place in the launch: tile tl of the tile list, row-major index r in the tile, frame
+// position (x, y), and its slot in the packed outputs
+struct ClaimPixel { uint32_t tl, r, x, y, slot; };
+__device__ __forceinline__ ClaimPixel tile_pixel(const KParams& kp, uint32_t tl, uint32_t lx, uint32_t ly) {
+  ClaimPixel c;
+  c.tl = tl; c.r = ly * kp.tile_size + lx;
+  c.x = kp.tiles[2 * tl] + lx; c.y = kp.tiles[2 * tl + 1] + ly;
+  c.slot = tl * (kp.tile_size * kp.tile_size) + c.r;
+  return c;
+}
+// Claim index ix < n_pixels (rrt_internal.h claim_r: the claim order within a tile).  ts: the
+// caller's kp.tile_size, for a kernel that holds it across its stages (rrt_batch_kernel)
+__device__ __forceinline__ ClaimPixel claim_pixel(const KParams& kp, uint32_t ix, uint32_t ts) {
+  const uint32_t tpix = ts * ts;
+  ClaimPixel c;
+  c.tl = kp.tile_order[ix / tpix]; c.r = claim_r(ix % tpix, ts);
+  const uint32_t lx = c.r % ts, ly = c.r / ts;
+  c.x = kp.tiles[2 * c.tl] + lx; c.y = kp.tiles[2 * c.tl + 1] + ly;
+  c.slot = c.tl * tpix + c.r;
+  return c;
+}
+__device__ __forceinline__ ClaimPixel claim_pixel(const KParams& kp, uint32_t ix) { return claim_pixel(kp, ix, kp.tile_size); }
+// Pixel k of the 8x8 block blk < n_blocks (the kernels that claim blocks of the tile list, not claim
+// indices); false: the block's pixel lies outside its tile
+__device__ __forceinline__ bool block_pixel(const KParams& kp, uint32_t blk, uint32_t k, ClaimPixel& c) {
+  const uint32_t bpt = kp.blocks_per_tile_side, b = blk % (bpt * bpt);
+  const uint32_t lx = (b % bpt) * 8 + (k & 7u), ly = (b / bpt) * 8 + (k >> 3);
+  c = tile_pixel(kp, blk / (bpt * bpt), lx, ly);
+  return lx < kp.tile_size && ly < kp.tile_size;
+}
+// The launch renders the pixels of its clip rectangle only.  (kp by pointer: a reference parameter is
+// known dereferenceable, the four reads then stop being short-circuit ones, and every caller's
+// register allocation moves)
+__device__ __forceinline__ bool in_clip(const KParams* kp, uint32_t x, uint32_t y) {
+  return x >= kp->clip_x0 && y >= kp->clip_y0 && x < kp->clip_x1 && y < kp->clip_y1;
+}
+
+// A pixel's result: radiance, samples taken, RNG draws (where the launch records them) ...
+__device__ __forceinline__ void write_pixel(const KParams& kp, uint32_t slot, spec rgb, int32_t count, uint32_t draws) {
+  kp.rgb[3 * slot] = rgb.r; kp.rgb[3 * slot + 1] = rgb.g; kp.rgb[3 * slot + 2] = rgb.b;
+  kp.count[slot] = count;
+  if (kp.draws) kp.draws[slot] = draws;
+}
+// ... its work counters (the COUNT builds, where the launch records them) ...
+__device__ __forceinline__ void write_counters(const KParams& kp, uint32_t slot, const Counters& cn) {
+  if (!kp.counters) return;
+  kp.counters[4 * slot] = cn.bbox; kp.counters[4 * slot + 1] = cn.micro;
+  kp.counters[4 * slot + 2] = cn.prim; kp.counters[4 * slot + 3] = cn.query;
+}
+// ... and the result of a pixel whose every camera ray is a proven miss (no environment map): its
+// samples are all zero, so it stops at the first adaptive check or at ns_aa, every sample a miss
+__device__ __forceinline__ void write_proven_pixel(const KParams& kp, uint32_t slot) {
+  const uint32_t n = min(kp.ns_aa, kp.samples_per_batch);
+  write_pixel(kp, slot, S(0.0f, 0.0f, 0.0f), (int32_t)n, n * kp.draws_miss);
+}
+
 // ------------------------------------------------------------------ pixel miss proof
 // (DESIGN.md §5).  Every camera ray of pixel (px, py) -- jitter anywhere in the pixel's square,
 // part1_code.cpp:182-187 -- is a proven miss.  All the rays start at the camera position O, so
@@ -1726,13 +1824,6 @@ __device__ __forceinline__ bool camera_proven_miss(const KParams& kp, v3 o, v3 d
 // the same for all, |P - P_c| <= rho |1/v - 1/v_c| + (rho / |v|) |eb| |y - y_c|.  Each segment
 // of the central ray must then clear the root box by the camera proof's margin plus that bound.
 // Launch constants are the camera proof's (KParams::miss) and the camera's.
-__device__ __forceinline__ v3 pixel_ray_dir(const KParams& kp, double sx, double sy) {
-  const DCamera& cam = kp.cam;
-  const double cx = sx / kp.frame_w, cy = sy / kp.frame_h;
-  const double vx = (1 - cx) * cam.blx + cx * -cam.blx, vy = (1 - cy) * cam.bly + cy * -cam.bly;
-  const v3 w = (smul(vx, ld3(cam.c2w0)) + smul(vy, ld3(cam.c2w1))) + smul(-1.0, ld3(cam.c2w2));
-  return unit(w);
-}
 // A rectangle of pixels (the strip pass, rrt_strip_proof_kernel): jitter positions [px, px + w] x
 // [py, py + h]; the same argument with the rectangle's corners and centre (the curvature term
 // uses its half-diagonal, so it holds for any small rectangle; w = h = 1 is pixel_miss_proof).

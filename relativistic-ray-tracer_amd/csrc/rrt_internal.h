@@ -1,5 +1,6 @@
-// rrt_internal.h -- device data layout shared by the host side (rrt_host.cpp) and the
-// kernels (rrt_kernel.hip).  See DESIGN.md "Data layout in HBM".
+// rrt_internal.h -- device data layout shared by the host side (rrt_host.cpp) and the four
+// kernel units (rrt_kernel.hip, rrt_sample.hip, rrt_path.hip, rrt_query.hip, through rrt_device.h).
+// See DESIGN.md "Data layout in HBM".
 #pragma once
 #include <stdint.h>
 

@@ -57,6 +57,8 @@ __device__ __forceinline__ spec raytrace_pixel(const KParams& kp, uint32_t x, ui
               // `++i; break;` form was miscompiled in the register-starved bounce build)
   double s1 = 0.0, s2 = 0.0;
   const DCamera& cam = kp.cam;
+  // (this loop restates rrt_device.h sample_pos, sensor_point / pixel_ray_dir and adaptive_stop: through
+  // the helpers m3 ran 1.1 % slower, outside the parent's spread -- profiles/rules_once_ab.txt)
   for (int i = 0; i < (int)kp.ns_aa; ++i) {
     double sx = (double)x, sy = (double)y;
     if (kp.ns_aa == 1) { sx += 0.5; sy += 0.5; }
@@ -120,6 +122,7 @@ __global__ __launch_bounds__(256, WAVES) void rrt_render_kernel(const KParams* _
     uint32_t blk = 0;
     if (lane == 0) blk = atomicAdd(kp.block_counter, kp.claim_list ? 64u : 1u);
     blk = __shfl(blk, 0);
+    // (restates rrt_device.h claim_pixel / block_pixel, in_clip and write_pixel / write_counters, as above)
     uint32_t t, lx, ly;
     bool mine;
     if (kp.claim_list) {  // the pixel proof pass's list: 64 listed pixels per claim, one per lane

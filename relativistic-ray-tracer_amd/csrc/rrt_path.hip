@@ -43,16 +43,7 @@ struct PathLds {
   uint8_t cam[256];   // R1 is a camera ray
 };
 
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-// volatile LDS-qualified accesses (ds_read / ds_write; a pointer that is not LDS does not compile)
-template <class T>
-__device__ __forceinline__ void pput(RRT_LDS T* a, uint32_t i, T v) { lput(a, i, v); }
-template <class T>
-__device__ __forceinline__ T pget(const RRT_LDS T* a, uint32_t i) { return lget(a, i); }
+// (wave_sync, lput / lget: rrt_device.h)
 
 // the n-th (from 0) set bit of m; n < popcount(m)
 __device__ __forceinline__ uint32_t nth_bit(uint64_t m, uint32_t n) {
@@ -106,17 +97,12 @@ __device__ __forceinline__ uint32_t* rec(const KParams& kp, uint32_t field) {
 // Camera::generate_ray at the sample's jitter (part1_code.cpp:132-141, 182-187) into R1
 __device__ __forceinline__ void start_sample(const KParams& kp, Rng& g, uint32_t t) {
   RRT_LDS PathLds& pl = lds_of(rrt::pl_mem);
-  const DCamera& cam = kp.cam;
   const uint32_t pxy = *rec(kp, 0);
-  double sx = (double)(pxy & 0xffffu), sy = (double)(pxy >> 16);
-  if (kp.ns_aa == 1) { sx += 0.5; sy += 0.5; }
-  else { double jx, jy; g.grid(jx, jy); sx += jx; sy += jy; }
-  const double cx = sx / kp.frame_w, cy = sy / kp.frame_h;
-  const double vx = (1 - cx) * cam.blx + cx * -cam.blx, vy = (1 - cy) * cam.bly + cy * -cam.bly;
-  const v3 w = (smul(vx, ld3(cam.c2w0)) + smul(vy, ld3(cam.c2w1))) + smul(-1.0, ld3(cam.c2w2));
-  const v3 d = unit(w);
-  pput(pl.d1[0], t, d.x); pput(pl.d1[1], t, d.y); pput(pl.d1[2], t, d.z);
-  pput(pl.cam, t, (uint8_t)1u);
+  double sx, sy;
+  sample_pos(kp, g, pxy & 0xffffu, pxy >> 16, sx, sy);
+  const v3 d = pixel_ray_dir(kp, sx, sy);
+  lput(pl.d1[0], t, d.x); lput(pl.d1[1], t, d.y); lput(pl.d1[2], t, d.z);
+  lput(pl.cam, t, (uint8_t)1u);
 }
 
 // The path phase of one path whose rays are all back: consume their results and run the
@@ -131,16 +117,16 @@ __device__ __forceinline__ uint32_t path_phase(const KParams& kp, uint32_t st) {
   auto stk = [&](uint32_t lv, uint32_t field) -> float* { return rrt::stk(kp, lv, field); };
   auto rec = [&](uint32_t field) -> uint32_t* { return rrt::rec(kp, field); };
   bool p0 = false, p1 = false;
-  uint32_t fl = pget(ol.fl, t);
+  uint32_t fl = lget(ol.fl, t);
   bool r0_out = fl & F_R0, b_out = fl & F_BOUT, lights_drawn = fl & F_LDRAWN, decided = fl & F_DECIDED,
        dl = fl & F_DELTA;
   uint32_t k = (fl >> 12) & 15u, depth = (fl >> 16) & 31u, lj = fl >> 21, nsh = 0;
-  spec Lv = S(pget(ol.lv[0], t), pget(ol.lv[1], t), pget(ol.lv[2], t));
+  spec Lv = S(lget(ol.lv[0], t), lget(ol.lv[1], t), lget(ol.lv[2], t));
   const uint32_t pxy = *rec(0);
-  Rng g; g.key = rrt_pixel_key(kp.seed, pxy & 0xffffu, pxy >> 16); g.ctr = pget(ol.ctr, t);
+  Rng g; g.key = rrt_pixel_key(kp.seed, pxy & 0xffffu, pxy >> 16); g.ctr = lget(ol.ctr, t);
   auto vertex_begin = [&]() {  // the hit record in LDS is the vertex
     st = P_VTX;
-    dl = is_delta(kp.bsdfs[pget(pl.bsdf, t)]);
+    dl = is_delta(kp.bsdfs[lget(pl.bsdf, t)]);
     Lv = S(0, 0, 0);
     lj = 0;
     // depth >= 2 takes direct light only at non-delta vertices (:75-77); one_bounce_radiance
@@ -151,11 +137,11 @@ __device__ __forceinline__ uint32_t path_phase(const KParams& kp, uint32_t st) {
   bool fin = false;
   spec s = S(0, 0, 0);
   if (st == P_CAM) {  // est_radiance_global_illumination (:103-123) on the camera ray's result
-    if (!pget(pl.res1, t)) {
+    if (!lget(pl.res1, t)) {
       fin = true;
-      if (kp.env.w) s = env_dir(kp.env, V(pget(pl.d1[0], t), pget(pl.d1[1], t), pget(pl.d1[2], t)));
+      if (kp.env.w) s = env_dir(kp.env, V(lget(pl.d1[0], t), lget(pl.d1[1], t), lget(pl.d1[2], t)));
     } else {
-      const spec e0 = emission(kp.bsdfs[pget(pl.bsdf, t)]);
+      const spec e0 = emission(kp.bsdfs[lget(pl.bsdf, t)]);
       if (kp.max_ray_depth == 0) {
         fin = true;
         s = e0;
@@ -168,10 +154,10 @@ __device__ __forceinline__ uint32_t path_phase(const KParams& kp, uint32_t st) {
     }
   } else if (r0_out) {  // the outstanding direct-light ray's result
     r0_out = false;
-    const uint32_t r = pget(pl.res0, t);
-    const spec c3 = S(pget(ol.c3[0], t), pget(ol.c3[1], t), pget(ol.c3[2], t));
+    const uint32_t r = lget(pl.res0, t);
+    const spec c3 = S(lget(ol.c3[0], t), lget(ol.c3[1], t), lget(ol.c3[2], t));
     if (hemi) {
-      if (r) Lv = Lv + (emission(kp.bsdfs[r - 1u]) * c3) * pget(ol.cz, t);
+      if (r) Lv = Lv + (emission(kp.bsdfs[r - 1u]) * c3) * lget(ol.cz, t);
     } else if (!r) {
       Lv = Lv + c3;
     }
@@ -188,10 +174,10 @@ __device__ __forceinline__ uint32_t path_phase(const KParams& kp, uint32_t st) {
   while (!fin && st == P_VTX) {
     // the vertex's next light samples (:15-57) up to one that needs a ray (R0)
     while (!lights_drawn && lj < nsh) {
-      const v3 hp = V(pget(pl.hp[0], t), pget(pl.hp[1], t), pget(pl.hp[2], t));
-      const v3 nn = V(pget(pl.nn[0], t), pget(pl.nn[1], t), pget(pl.nn[2], t));
-      const v3 wo = V(pget(pl.wo[0], t), pget(pl.wo[1], t), pget(pl.wo[2], t));
-      const DBsdf b = kp.bsdfs[pget(pl.bsdf, t)];
+      const v3 hp = V(lget(pl.hp[0], t), lget(pl.hp[1], t), lget(pl.hp[2], t));
+      const v3 nn = V(lget(pl.nn[0], t), lget(pl.nn[1], t), lget(pl.nn[2], t));
+      const v3 wo = V(lget(pl.wo[0], t), lget(pl.wo[1], t), lget(pl.wo[2], t));
+      const DBsdf b = kp.bsdfs[lget(pl.bsdf, t)];
       const Frame f = coord_space(nn);
       const uint32_t jj = lj++;
       v3 wi;
@@ -200,7 +186,7 @@ __device__ __forceinline__ uint32_t path_phase(const KParams& kp, uint32_t st) {
         const v3 w_in = hemisphere_sample(g);
         wi = to_world(f, w_in);
         c3 = bsdf_f(b, to_local(f, wo), w_in);
-        pput(ol.cz, t, (float)w_in.z);
+        lput(ol.cz, t, (float)w_in.z);
       } else {
         uint32_t li = 0, r = jj;  // light and sample of flat index jj
         for (;; ++li) {
@@ -214,8 +200,8 @@ __device__ __forceinline__ uint32_t path_phase(const KParams& kp, uint32_t st) {
         if (w_in.z < 0) continue;
         c3 = ((smp * bsdf_f<0>(b, to_local(f, wo), w_in)) * (float)w_in.z) / pdf;
       }
-      pput(ol.c3[0], t, c3.r); pput(ol.c3[1], t, c3.g); pput(ol.c3[2], t, c3.b);
-      pput(pl.d0[0], t, wi.x); pput(pl.d0[1], t, wi.y); pput(pl.d0[2], t, wi.z);
+      lput(ol.c3[0], t, c3.r); lput(ol.c3[1], t, c3.g); lput(ol.c3[2], t, c3.b);
+      lput(pl.d0[0], t, wi.x); lput(pl.d0[1], t, wi.y); lput(pl.d0[2], t, wi.z);
       p0 = true;
       r0_out = true;
       break;
@@ -225,17 +211,17 @@ __device__ __forceinline__ uint32_t path_phase(const KParams& kp, uint32_t st) {
     if (lights_drawn && !decided) {
       decided = true;
       if (deep && (depth == kp.max_ray_depth || (depth > 1 && g.coin(0.7)))) {
-        const v3 nn = V(pget(pl.nn[0], t), pget(pl.nn[1], t), pget(pl.nn[2], t));
-        const v3 wo = V(pget(pl.wo[0], t), pget(pl.wo[1], t), pget(pl.wo[2], t));
-        const DBsdf b = kp.bsdfs[pget(pl.bsdf, t)];
+        const v3 nn = V(lget(pl.nn[0], t), lget(pl.nn[1], t), lget(pl.nn[2], t));
+        const v3 wo = V(lget(pl.wo[0], t), lget(pl.wo[1], t), lget(pl.wo[2], t));
+        const DBsdf b = kp.bsdfs[lget(pl.bsdf, t)];
         const Frame f = coord_space(nn);
         v3 w_in;
         float pdf;
         const spec smp = bsdf_sample_f(b, g, to_local(f, wo), w_in, pdf);
         if (pdf != 0.0f) {
           const v3 wi = to_world(f, w_in);
-          pput(pl.d1[0], t, wi.x); pput(pl.d1[1], t, wi.y); pput(pl.d1[2], t, wi.z);
-          pput(pl.cam, t, (uint8_t)0u);
+          lput(pl.d1[0], t, wi.x); lput(pl.d1[1], t, wi.y); lput(pl.d1[2], t, wi.z);
+          lput(pl.cam, t, (uint8_t)0u);
           p1 = true;
           b_out = true;
           *stk(k, 3) = smp.r; *stk(k, 4) = smp.g; *stk(k, 5) = smp.b;
@@ -252,8 +238,8 @@ __device__ __forceinline__ uint32_t path_phase(const KParams& kp, uint32_t st) {
       break;
     }
     Ld = dl ? S(0, 0, 0) : S(0, 0, 0) + Ld;
-    if (b_out && pget(pl.res1, t) && k + 1 < RRT_MAX_DEPTH) {  // the child level
-      const spec ce = emission(kp.bsdfs[pget(pl.bsdf, t)]);
+    if (b_out && lget(pl.res1, t) && k + 1 < RRT_MAX_DEPTH) {  // the child level
+      const spec ce = emission(kp.bsdfs[lget(pl.bsdf, t)]);
       *stk(k, 0) = Ld.r; *stk(k, 1) = Ld.g; *stk(k, 2) = Ld.b;
       *stk(k, 6) = ce.r; *stk(k, 7) = ce.g; *stk(k, 8) = ce.b;
       *stk(k, 11) = dl ? 1.0f : 0.0f;
@@ -283,16 +269,9 @@ __device__ __forceinline__ uint32_t path_phase(const KParams& kp, uint32_t st) {
     s1 += il;
     s2 += il * il;
     bool stop = n >= (int)kp.ns_aa;
-    if ((uint32_t)n % kp.samples_per_batch == 0) {  // ADAPTIVE 1
-      const double avg = s1 / n, sd = sqrt((s2 - avg * s1) / (n - 1));
-      if (1.96 * sd / sqrt((double)n) <= (double)kp.max_tolerance * avg) stop = true;
-    }
+    if ((uint32_t)n % kp.samples_per_batch == 0 && adaptive_stop(kp, s1, s2, n)) stop = true;
     if (stop) {
-      const uint32_t slot = *rec(1);
-      const spec r = ret / (float)n;
-      kp.rgb[3 * slot] = r.r; kp.rgb[3 * slot + 1] = r.g; kp.rgb[3 * slot + 2] = r.b;
-      kp.count[slot] = n;
-      if (kp.draws) kp.draws[slot] = g.ctr;
+      write_pixel(kp, *rec(1), ret / (float)n, n, g.ctr);
       st = P_IDLE;
     } else {
       *(float*)rec(3) = ret.r; *(float*)rec(4) = ret.g; *(float*)rec(5) = ret.b;
@@ -304,10 +283,10 @@ __device__ __forceinline__ uint32_t path_phase(const KParams& kp, uint32_t st) {
       st = P_CAM;
     }
   }
-  pput(ol.fl, t, (r0_out ? F_R0 : 0u) | (b_out ? F_BOUT : 0u) | (lights_drawn ? F_LDRAWN : 0u) |
+  lput(ol.fl, t, (r0_out ? F_R0 : 0u) | (b_out ? F_BOUT : 0u) | (lights_drawn ? F_LDRAWN : 0u) |
                      (decided ? F_DECIDED : 0u) | (dl ? F_DELTA : 0u) | (k << 12) | (depth << 16) | (lj << 21));
-  pput(ol.lv[0], t, Lv.r); pput(ol.lv[1], t, Lv.g); pput(ol.lv[2], t, Lv.b);
-  pput(ol.ctr, t, g.ctr);
+  lput(ol.lv[0], t, Lv.r); lput(ol.lv[1], t, Lv.g); lput(ol.lv[2], t, Lv.b);
+  lput(ol.ctr, t, g.ctr);
   return st | (p0 ? 16u : 0u) | (p1 ? 32u : 0u);
 }
 
@@ -350,7 +329,6 @@ __global__ __launch_bounds__(256, WAVES) void rrt_path_kernel(const KParams* __r
     // they would all stay live (in VGPRs, once the SGPRs run out) across the query
     asm volatile("" : "+s"(kpp));
     const KParams& kp = *(const KParams*)kpp;
-    const uint32_t ts = kp.tile_size, tpix = ts * ts;
     const bool hemi = kp.direct_hemisphere != 0;
     const DCamera& cam = kp.cam;
     auto rec = [&](uint32_t field) -> uint32_t* { return rrt::rec(kp, field); };
@@ -382,11 +360,11 @@ __global__ __launch_bounds__(256, WAVES) void rrt_path_kernel(const KParams* __r
         } else {
           const uint32_t ix = kp.claim_list ? (kp.claim_list[c] & 0x7fffffffu) : c;
           const uint32_t pi = ix < kp.n_pixels ? ix : 0u;
-          const uint32_t tl = kp.tile_order[pi / tpix], r = claim_r(pi % tpix, ts);
-          const uint32_t x = kp.tiles[2 * tl] + r % ts, y = kp.tiles[2 * tl + 1] + r / ts;
-          if (ix < kp.n_pixels && x >= kp.clip_x0 && y >= kp.clip_y0 && x < kp.clip_x1 && y < kp.clip_y1) {
+          const ClaimPixel c = claim_pixel(kp, pi);
+          const uint32_t x = c.x, y = c.y;
+          if (ix < kp.n_pixels && in_clip(&kp, x, y)) {
             *rec(0) = x | (y << 16);
-            *rec(1) = tl * tpix + r;
+            *rec(1) = c.slot;
             *rec(2) = 0u;
             *(float*)rec(3) = 0.0f; *(float*)rec(4) = 0.0f; *(float*)rec(5) = 0.0f;
             *rec(6) = 0u; *rec(7) = 0u; *rec(8) = 0u; *rec(9) = 0u;
@@ -394,8 +372,8 @@ __global__ __launch_bounds__(256, WAVES) void rrt_path_kernel(const KParams* __r
             start_sample(kp, g, t);
             p1 = true;
             st = P_CAM;
-            pput(ol.ctr, t, g.ctr);
-            pput(ol.fl, t, 0u);
+            lput(ol.ctr, t, g.ctr);
+            lput(ol.fl, t, 0u);
           }
         }
       }
@@ -432,13 +410,13 @@ __global__ __launch_bounds__(256, WAVES) void rrt_path_kernel(const KParams* __r
     if (rp < 64u) {
       const uint32_t q = wb + rp;
       if (rs1) {
-        d = V(pget(pl.d1[0], q), pget(pl.d1[1], q), pget(pl.d1[2], q));
-        cray = pget(pl.cam, q) != 0u;
+        d = V(lget(pl.d1[0], q), lget(pl.d1[1], q), lget(pl.d1[2], q));
+        cray = lget(pl.cam, q) != 0u;
       } else {
-        d = V(pget(pl.d0[0], q), pget(pl.d0[1], q), pget(pl.d0[2], q));
+        d = V(lget(pl.d0[0], q), lget(pl.d0[1], q), lget(pl.d0[2], q));
         any = !hemi;
       }
-      o = cray ? ld3(cam.pos) : V(pget(pl.hp[0], q), pget(pl.hp[1], q), pget(pl.hp[2], q)) + smul(EPS_D, d);
+      o = cray ? ld3(cam.pos) : V(lget(pl.hp[0], q), lget(pl.hp[1], q), lget(pl.hp[2], q)) + smul(EPS_D, d);
     }
     wave_sync();
     Isect is;
@@ -454,15 +432,15 @@ __global__ __launch_bounds__(256, WAVES) void rrt_path_kernel(const KParams* __r
       if (!known) h = query<false, false, false, false>(kp, o, d, &is, cn, any);
       const uint32_t q = wb + rp;
       if (rs1) {
-        pput(pl.res1, q, (uint8_t)(h ? 1u : 0u));
+        lput(pl.res1, q, (uint8_t)(h ? 1u : 0u));
         if (h) {
-          pput(pl.hp[0], q, is.hit_p.x); pput(pl.hp[1], q, is.hit_p.y); pput(pl.hp[2], q, is.hit_p.z);
-          pput(pl.nn[0], q, is.n.x); pput(pl.nn[1], q, is.n.y); pput(pl.nn[2], q, is.n.z);
-          pput(pl.wo[0], q, is.w_out.x); pput(pl.wo[1], q, is.w_out.y); pput(pl.wo[2], q, is.w_out.z);
-          pput(pl.bsdf, q, (uint8_t)is.bsdf);
+          lput(pl.hp[0], q, is.hit_p.x); lput(pl.hp[1], q, is.hit_p.y); lput(pl.hp[2], q, is.hit_p.z);
+          lput(pl.nn[0], q, is.n.x); lput(pl.nn[1], q, is.n.y); lput(pl.nn[2], q, is.n.z);
+          lput(pl.wo[0], q, is.w_out.x); lput(pl.wo[1], q, is.w_out.y); lput(pl.wo[2], q, is.w_out.z);
+          lput(pl.bsdf, q, (uint8_t)is.bsdf);
         }
       } else {
-        pput(pl.res0, q, (uint8_t)(any ? (h ? 1u : 0u) : (h ? (uint32_t)is.bsdf + 1u : 0u)));
+        lput(pl.res0, q, (uint8_t)(any ? (h ? 1u : 0u) : (h ? (uint32_t)is.bsdf + 1u : 0u)));
       }
     }
     wave_sync();

@@ -160,6 +160,28 @@ extern "C" int rrt_prof_read(unsigned long long* out) {  // out: RRT_PROF_HDR + 
   unsigned long long z[RRT_PROF_HDR] = {0, 0, 0, 0, 0, 0, 0, 0, ~0ull, 0, 0, ~0ull, 0, 0, 0, 0, 0, 0, 0, 0};
   return hipMemcpyToSymbol(HIP_SYMBOL(rrt_prof), z, sizeof(z)) == hipSuccess ? 0 : -1;
 }
+// A wave's epilogue: wave time per phase ~ the busiest lane's, summed over waves (v[0..7] to
+// rrt_prof[0..7], the batch kernel's v[8..] to [16..]; tools/phase_profile.py), then the wave's
+// start / end / work record
+template <int NV>
+__device__ __forceinline__ void prof_wave_record(uint64_t (&v)[NV], uint32_t lane, uint64_t w_start, uint64_t w_end,
+                                                 unsigned long long work) {
+  for (int k = 0; k < NV; ++k) {
+    for (int off = 32; off > 0; off >>= 1) {
+      const uint64_t o2 = __shfl_xor(v[k], off);
+      v[k] = v[k] > o2 ? v[k] : o2;
+    }
+    if (lane == 0) atomicAdd(&rrt_prof[k < 8 ? k : k + 8], (unsigned long long)v[k]);
+  }
+  if (lane == 0) {  // [8] min start, [9] max end, [10] waves; per-wave records
+    atomicMin(&rrt_prof[8], (unsigned long long)w_start);
+    atomicMax(&rrt_prof[9], (unsigned long long)w_end);
+    const unsigned long long w = atomicAdd(&rrt_prof[10], 1ull) & 16383;
+    rrt_prof_ends[w] = w_end;
+    rrt_prof_starts[w] = w_start;
+    rrt_prof_work[w] = work;
+  }
+}
 #endif
 
 // COUNT: per-pixel work counters; LEAN: area/point lights only, no microfacet BSDF, importance-sampled
@@ -175,8 +197,6 @@ __global__ __launch_bounds__(256, WAVES) void rrt_sample_kernel(const KParams* _
   const uint32_t t = threadIdx.x;
   const uint32_t lane = t & 63u;
   const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64u - lane));
-  const uint32_t bpt = kp.blocks_per_tile_side;
-  const uint32_t tpix = kp.tile_size * kp.tile_size;
   const DCamera& cam = kp.cam;
 
   uint32_t pool_blk = 0, pool_next = 64;  // wave-uniform pixel pool (one 8x8 block)
@@ -219,24 +239,18 @@ __global__ __launch_bounds__(256, WAVES) void rrt_sample_kernel(const KParams* _
       const uint32_t rank = (uint32_t)__popcll(need & lt_mask);
       if (!have && rank < avail) {
         const uint32_t k = pool_next + rank;
-        uint32_t tl, lx, ly;
-        bool listed = true;
+        ClaimPixel c;
+        bool mine;
         if (kp.claim_list) {
           const uint32_t e = pool_blk * 64u + k;
-          listed = e < *kp.claim_count;
-          const uint32_t ix = listed ? (kp.claim_list[e] & 0x7fffffffu) : 0u;
-          tl = kp.tile_order[ix / tpix];
-          const uint32_t r = claim_r(ix % tpix, kp.tile_size);
-          lx = r % kp.tile_size; ly = r / kp.tile_size;
+          mine = e < *kp.claim_count;
+          c = claim_pixel(kp, mine ? (kp.claim_list[e] & 0x7fffffffu) : 0u);
         } else {
-          tl = pool_blk / (bpt * bpt);
-          const uint32_t b = pool_blk % (bpt * bpt);
-          lx = (b % bpt) * 8 + (k & 7u); ly = (b / bpt) * 8 + (k >> 3);
+          mine = block_pixel(kp, pool_blk, k, c);
         }
-        const uint32_t x = kp.tiles[2 * tl] + lx, y = kp.tiles[2 * tl + 1] + ly;
-        if (listed && lx < kp.tile_size && ly < kp.tile_size && x >= kp.clip_x0 && y >= kp.clip_y0 && x < kp.clip_x1 &&
-            y < kp.clip_y1) {
-          px = x; py = y; slot = tl * tpix + ly * kp.tile_size + lx;
+        const uint32_t x = c.x, y = c.y;
+        if (mine && in_clip(&kp, x, y)) {
+          px = x; py = y; slot = c.slot;
           g.key = rrt_pixel_key(kp.seed, x, y); g.ctr = 0;
           i = 0;
           cn.bbox = 0; cn.micro = 0; cn.prim = 0; cn.query = 0;
@@ -250,16 +264,15 @@ __global__ __launch_bounds__(256, WAVES) void rrt_sample_kernel(const KParams* _
           if (COUNT && kp.audit && kp.miss.on &&
               (rrt_mix64(g.key) & ((1ull << kp.audit_shift) - 1ull)) == 0ull) {
             if (pixel_miss_proof(kp, x, y)) aud |= 1u;
-            const uint32_t sx = kp.tiles[2 * tl] + (lx & ~7u), sy = kp.tiles[2 * tl + 1] + (ly & ~7u);
+            const uint32_t lx = c.r % kp.tile_size, ly = c.r / kp.tile_size;  // the pixel's 8x8 strip
+            const uint32_t sx = kp.tiles[2 * c.tl] + (lx & ~7u), sy = kp.tiles[2 * c.tl + 1] + (ly & ~7u);
             if (sx >= kp.clip_x0 && sy >= kp.clip_y0 && sx + 8u <= kp.clip_x1 && sy + 8u <= kp.clip_y1 &&
                 rect_miss_proof(kp, (double)sx, (double)sy, 8.0, 8.0))
               aud |= 2u;
           }
           if (kp.ns_aa == 0) {  // the reference's loop does not run: ret / 0, count 0
             const float r = 0.0f / (float)0;
-            kp.rgb[3 * slot] = r; kp.rgb[3 * slot + 1] = r; kp.rgb[3 * slot + 2] = r;
-            kp.count[slot] = 0;
-            if (kp.draws) kp.draws[slot] = 0;
+            write_pixel(kp, slot, S(r, r, r), 0, 0u);
             have = false;
           }
         }
@@ -271,16 +284,12 @@ __global__ __launch_bounds__(256, WAVES) void rrt_sample_kernel(const KParams* _
     if (!have) continue;
 
     // ---- one camera sample (raytrace_pixel loop body, part1_code.cpp:131-159)
-    double sx = (double)px, sy = (double)py;
-    if (kp.ns_aa == 1) { sx += 0.5; sy += 0.5; }
-    else { double jx, jy; g.grid(jx, jy); sx += jx; sy += jy; }
-    const double cx = sx / kp.frame_w, cy = sy / kp.frame_h;  // Camera::generate_ray (:182-187)
-    const double vx = (1 - cx) * cam.blx + cx * -cam.blx, vy = (1 - cy) * cam.bly + cy * -cam.bly;
-    const v3 w = (smul(vx, ld3(cam.c2w0)) + smul(vy, ld3(cam.c2w1))) + smul(-1.0, ld3(cam.c2w2));
+    double sx, sy;
+    sample_pos(kp, g, px, py, sx, sy);
     spec s = S(0, 0, 0);
     {
       Isect is;
-      const v3 wd = unit(w);
+      const v3 wd = pixel_ray_dir(kp, sx, sy);
       if (!camera_proven_miss<COUNT, LEAN == V_KERR>(kp, ld3(cam.pos), wd, cn) &&
           query<false, COUNT, LEAN == V_KERR, is_lean(LEAN)>(kp, ld3(cam.pos), wd, &is, cn)) {  // est_radiance (:103-123)
         const spec e = emission(kp.bsdfs[is.bsdf]);
@@ -290,7 +299,7 @@ __global__ __launch_bounds__(256, WAVES) void rrt_sample_kernel(const KParams* _
         else if (kp.direct_hemisphere) s = e + direct_hemisphere_lds<COUNT, LEAN>(kp, g, is, cl, t, cn);
         else s = e + direct_importance_lds<COUNT, LEAN, RRT_OCC_TAG_S(COUNT, LEAN, WAVES)>(kp, g, is, cl, t, cn);
       } else if (!is_lean(LEAN) && kp.env.w) {
-        s = env_dir(kp.env, unit(w));  // miss: envLight->sample_dir of the unbent camera ray
+        s = env_dir(kp.env, pixel_ray_dir(kp, sx, sy));  // miss: envLight->sample_dir of the unbent camera ray
       }
       if (COUNT && aud) {  // the pixel pass's proofs say this camera ray misses
         Counters c2 = {};
@@ -308,19 +317,10 @@ __global__ __launch_bounds__(256, WAVES) void rrt_sample_kernel(const KParams* _
     ++prof_samples;
 #endif
     bool stop = i >= (int)kp.ns_aa;
-    if ((uint32_t)i % kp.samples_per_batch == 0) {  // ADAPTIVE == 1 (:147-158)
-      const double avg = s1 / i, sd = sqrt((s2 - avg * s1) / (i - 1));
-      if (1.96 * sd / sqrt((double)i) <= (double)kp.max_tolerance * avg) stop = true;
-    }
+    if ((uint32_t)i % kp.samples_per_batch == 0 && adaptive_stop(kp, s1, s2, i)) stop = true;
     if (stop) {
-      const spec r = ret / (float)i;
-      kp.rgb[3 * slot] = r.r; kp.rgb[3 * slot + 1] = r.g; kp.rgb[3 * slot + 2] = r.b;
-      kp.count[slot] = i;
-      if (kp.draws) kp.draws[slot] = g.ctr;
-      if (COUNT && kp.counters) {
-        kp.counters[4 * slot] = cn.bbox; kp.counters[4 * slot + 1] = cn.micro;
-        kp.counters[4 * slot + 2] = cn.prim; kp.counters[4 * slot + 3] = cn.query;
-      }
+      write_pixel(kp, slot, ret / (float)i, i, g.ctr);
+      if (COUNT) write_counters(kp, slot, cn);
       have = false;
     } else {
       lput(cl.s1, t, s1); lput(cl.s2, t, s2);
@@ -328,26 +328,11 @@ __global__ __launch_bounds__(256, WAVES) void rrt_sample_kernel(const KParams* _
     }
   }
 #if RRT_PROFILE
-  // wave time per phase ~ the busiest lane's; summed over waves (tools/phase_profile.py)
   const uint64_t t_end = clock64(), w_end = wall_clock64();
   uint64_t v[8] = {t_end - t_start, cn.t_query, cn.t_micro, cn.t_trav, cn.t_proof, cn.t_squery, cn.t_strav, 0};
-  for (int k = 0; k < 8; ++k) {
-    for (int off = 32; off > 0; off >>= 1) {
-      const uint64_t o2 = __shfl_xor(v[k], off);
-      v[k] = v[k] > o2 ? v[k] : o2;
-    }
-    if (lane == 0) atomicAdd(&rrt_prof[k], (unsigned long long)v[k]);
-  }
   uint32_t ns = prof_samples;
   for (int off = 32; off > 0; off >>= 1) ns += __shfl_xor(ns, off);
-  if (lane == 0) {  // [4] min start, [5] max end, [6] waves, [7] first exhaustion; per-wave records
-    atomicMin(&rrt_prof[8], (unsigned long long)w_start);
-    atomicMax(&rrt_prof[9], (unsigned long long)w_end);
-    const unsigned long long w = atomicAdd(&rrt_prof[10], 1ull) & 16383;
-    rrt_prof_ends[w] = w_end;
-    rrt_prof_starts[w] = w_start;
-    rrt_prof_work[w] = ((unsigned long long)prof_blocks << 32) | ns;
-  }
+  prof_wave_record(v, lane, w_start, w_end, ((unsigned long long)prof_blocks << 32) | ns);
 #endif
 }
 
@@ -408,8 +393,10 @@ struct GroupLds {  // group size >= 8: at most 32 groups per 256-thread block
 // it doubled the group loop's spills (cfg3 batch kernel 17.3 -> 33.5 ms), hence its own kernel.
 // The same block also takes continuations (ContRec, from the batch kernel): a pixel some of whose
 // steps are already folded, resumed from its sums and draw offset.
-// LDS: the parked hit records (ShadeLdsN, the batch kernel's own `cl` when its blocks take
-// continuations) and HeavyState (over the batch kernel's group records there).
+// LDS (HeavyLds, the heavy kernel's one __shared__ object): `sh`, the 64 NW parked hit records of the
+// round's slots (ShadeLdsN; its cr / cg / cb park a light sample's contribution across the shadow
+// query), and `hs` (HeavyState): each slot's sample radiance, each wave's ballot of hits, and the
+// claimed pixel.
 template <int NW>
 struct HeavyState {
   float r[64 * NW], g[64 * NW], b[64 * NW];  // each slot's sample radiance
@@ -429,10 +416,8 @@ struct HeavyLds {
 // Thread 0: the pixel proof pass's heavy-list entry k as a fresh pixel
 template <int NW>
 __device__ __forceinline__ void heavy_take_listed(const KParams& kp, HeavyState<NW>& hs, uint32_t k) {
-  const uint32_t ts = kp.tile_size, tpix = ts * ts;
-  const uint32_t ix = kp.heavy_list[k];
-  const uint32_t tl = kp.tile_order[ix / tpix], r = claim_r(ix % tpix, ts);
-  hs.x = kp.tiles[2 * tl] + r % ts; hs.y = kp.tiles[2 * tl + 1] + r / ts; hs.slot = tl * tpix + r;
+  const rrt::ClaimPixel c = rrt::claim_pixel(kp, kp.heavy_list[k]);
+  hs.x = c.x; hs.y = c.y; hs.slot = c.slot;
   hs.i = 0; hs.m0 = 0; hs.r0 = 0.0f; hs.g0 = 0.0f; hs.b0 = 0.0f; hs.s1 = 0.0; hs.s2 = 0.0;
 }
 // Thread 0: continuation record h once its writer has published it (seq), as the pixel to resume
@@ -507,12 +492,8 @@ __device__ __noinline__ void heavy_pixel_block(const RRT_CONST_AS KParams* kpq, 
     const uint32_t lim = S1 * (kp.ns_aa - i);
     const uint32_t sl = m0 + t;
     Rng g; g.key = key; g.ctr = sl * Dm;
-    double jx, jy; g.grid(jx, jy);  // Camera::generate_ray (part1_code.cpp:182-187) at the slot's jitter
-    const double sx = (double)x + jx, sy = (double)y + jy;
-    const double cx = sx / kp.frame_w, cy = sy / kp.frame_h;
-    const double vx = (1 - cx) * cam.blx + cx * -cam.blx, vy = (1 - cy) * cam.bly + cy * -cam.bly;
-    const v3 w = (smul(vx, ld3(cam.c2w0)) + smul(vy, ld3(cam.c2w1))) + smul(-1.0, ld3(cam.c2w2));
-    const v3 wd = unit(w);
+    double jx, jy; g.grid(jx, jy);  // the camera ray at the slot's jitter
+    const v3 wd = pixel_ray_dir(kp, (double)x + jx, (double)y + jy);
     Isect is;
     const bool hit = t < lim && !camera_proven_miss<false, false>(kp_fresh(kp), ld3(cam.pos), wd, cn) &&
                      query_nx<false, false, false, 0, true, true>(kp, ld3(cam.pos), wd, &is, cn);
@@ -542,22 +523,14 @@ __device__ __noinline__ void heavy_pixel_block(const RRT_CONST_AS KParams* kpq, 
       ++i;
       m += ((hs.hits[m >> 6] >> (m & 63u)) & 1ull) ? S1 : 1u;
       st = i >= kp.ns_aa;
-      if (i % kp.samples_per_batch == 0) {  // ADAPTIVE == 1 (:147-158)
-        const double avg = s1 / i, sd = sqrt((s2 - avg * s1) / (i - 1));
-        if (1.96 * sd / sqrt((double)i) <= (double)kp.max_tolerance * avg) st = true;
-      }
+      if (i % kp.samples_per_batch == 0 && adaptive_stop(kp, s1, s2, i)) st = true;
       if (st) break;
     }
     m0 += m;
     __syncthreads();  // the fold's reads before the next round's writes
     if (st) break;
   }
-  if (t == 0) {
-    const spec rr = ret / (float)i;
-    kp.rgb[3 * slot] = rr.r; kp.rgb[3 * slot + 1] = rr.g; kp.rgb[3 * slot + 2] = rr.b;
-    kp.count[slot] = (int32_t)i;
-    if (kp.draws) kp.draws[slot] = m0 * Dm;
-  }
+  if (t == 0) write_pixel(kp, slot, ret / (float)i, (int32_t)i, m0 * Dm);
 }
 
 // The heavy pixels' kernel (heavy pixels), launched after the pixel proof pass on
@@ -700,7 +673,7 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
   const uint32_t gl = lane & (G - 1u);
   const uint32_t gbase = lane - gl;
   const uint32_t gid = t / G;  // group slot in GroupLds
-  const uint32_t ts = kp->tile_size, tpix = ts * ts;
+  const uint32_t ts = kp->tile_size;
   const uint32_t Dm = kp->draws_miss, Dh = kp->draws_hit;
   Counters cn = {};
 #if RRT_PROFILE
@@ -805,13 +778,12 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
                              : kp->n_pixels;
         const uint32_t ix = kp->claim_list ? (ent & 0x7fffffffu) : ent;
         const uint32_t pi = ix < kp->n_pixels ? ix : 0u;
-        const uint32_t tl = kp->tile_order[pi / tpix], r = claim_r(pi % tpix, ts), lx = r % ts, ly = r / ts;
-        const uint32_t x = kp->tiles[2 * tl] + lx, y = kp->tiles[2 * tl + 1] + ly;
-        if (ix < kp->n_pixels && x >= kp->clip_x0 && y >= kp->clip_y0 && x < kp->clip_x1 && y < kp->clip_y1) {
+        const ClaimPixel c = claim_pixel(*kp, pi, ts);
+        if (ix < kp->n_pixels && in_clip(&*kp, c.x, c.y)) {
           if (gl == 0) {
-            const uint32_t slot = tl * tpix + r;
-            lput(gs.px, gid, x); lput(gs.py, gid, y); lput(gs.slot, gid, slot);
-            lput(gs.key, gid, rrt_pixel_key(kp->seed, x, y));
+            const uint32_t slot = c.slot;
+            lput(gs.px, gid, c.x); lput(gs.py, gid, c.y); lput(gs.slot, gid, slot);
+            lput(gs.key, gid, rrt_pixel_key(kp->seed, c.x, c.y));
             if (kp->first) {  // sample 0 from rrt_first_kernel; its hit status is the hypothesis
               const KParams::FirstSample f0 = kp->first[slot];
               const spec s0 = S(f0.r, f0.g, f0.b);
@@ -854,9 +826,7 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
       else __builtin_amdgcn_s_setprio(0);
     };
     tail_prio();
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
 
     // ---- camera queries by draw-offset slot.  Sample k of the step starts at draw offset
     // O + Dm * m_k, where slot m_0 = 0 and m_{k+1} = m_k + (hit_k ? Dh / Dm : 1): a slot's ray
@@ -873,15 +843,13 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
     const uint32_t S1 = Dh / Dm;  // slots a hit consumes
     const uint32_t O0 = lget(gs.O, gid);
     for (uint32_t m = gl; m < RRT_SLOTS; m += G) lput(&gs.sst[gid][0], m, (uint8_t)0);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
     uint32_t my = RRT_SLOTS;  // slot to compute this round (RRT_SLOTS: none)
     if (have && (int)gl < left) {
       const uint32_t m0 = gl * (lget(gs.hyp, gid) ? S1 : 1u);
       if (m0 < RRT_SLOTS) my = m0;
     }
-    // the camera query of slot sl (Camera::generate_ray, part1_code.cpp:182-187, at its jitter)
+    // the camera query of slot sl (pixel_ray_dir at its jitter)
     // prove: run the miss proof in front of the exact march.  It pays only where the ray is expected
     // to miss: a ray that enters the root box cannot be proven, and its proof runs up to the entry
     // row before the march starts again from row 0 (DESIGN.md §5 "Proof gate").
@@ -889,11 +857,7 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
       const DCamera& cam = kp->cam;
       Rng g; g.key = lget(gs.key, gid); g.ctr = O0 + sl * Dm;
       double jx, jy; g.grid(jx, jy);
-      const double sx = (double)lget(gs.px, gid) + jx, sy = (double)lget(gs.py, gid) + jy;
-      const double cx = sx / kp->frame_w, cy = sy / kp->frame_h;
-      const double vx = (1 - cx) * cam.blx + cx * -cam.blx, vy = (1 - cy) * cam.bly + cy * -cam.bly;
-      const v3 w = (smul(vx, ld3(cam.c2w0)) + smul(vy, ld3(cam.c2w1))) + smul(-1.0, ld3(cam.c2w2));
-      const v3 wd = unit(w);
+      const v3 wd = pixel_ray_dir(*kp, (double)lget(gs.px, gid) + jx, (double)lget(gs.py, gid) + jy);
       // (the miss proof's constants are live inside it only; query renews its own)
       if (prove && camera_proven_miss<false, LEAN == V_KERR>(kp_stage<SC>(*kp), ld3(cam.pos), wd, cn)) return false;
       return query_nx<false, false, LEAN == V_KERR, 0, is_lean(LEAN), SC>(*kp, ld3(cam.pos), wd, is, cn);
@@ -926,14 +890,10 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
         is0.w_out = V(lget(cl.wo[0], src), lget(cl.wo[1], src), lget(cl.wo[2], src));
         is0.bsdf = (int)lget(cl.bsdf, src);
       }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_sync();
       if (requery && lost) slot_query(mk, &is0, true);
       if (move || (requery && lost)) park_hit(cl, t, is0);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_sync();
       return lost ? mk : RRT_SLOTS;
     };
     bool fin = false;  // the LEAN builds' last round: the given-up records, after the moves
@@ -975,9 +935,7 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
           hk = h;
         }
       }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_sync();
       my = RRT_SLOTS;
       if (fin) break;
       if (resolved) continue;
@@ -1022,9 +980,7 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
         if (my < RRT_SLOTS && free_b) lput(&gs.sst[gid][0], held, (uint8_t)3);
       }
       RRT_ACC(t_chain, tw0);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_sync();
     }
     const bool act = have && (int)gl < n_step;
     const bool hit = act && hk;
@@ -1040,14 +996,9 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
     stage();
     spec s = S(0, 0, 0);
     if (!is_lean(LEAN) && act && !hit && kp->env.w) {  // miss: envLight->sample_dir of the unbent camera ray
-      const DCamera& cam = kp->cam;
       Rng g; g.key = lget(gs.key, gid); g.ctr = off;  // re-derive the ray from its jitter draws
       double jx, jy; g.grid(jx, jy);
-      const double sx = (double)lget(gs.px, gid) + jx, sy = (double)lget(gs.py, gid) + jy;
-      const double cx = sx / kp->frame_w, cy = sy / kp->frame_h;
-      const double vx = (1 - cx) * cam.blx + cx * -cam.blx, vy = (1 - cy) * cam.bly + cy * -cam.bly;
-      const v3 w = (smul(vx, ld3(cam.c2w0)) + smul(vy, ld3(cam.c2w1))) + smul(-1.0, ld3(cam.c2w2));
-      s = env_dir(kp->env, unit(w));
+      s = env_dir(kp->env, pixel_ray_dir(*kp, (double)lget(gs.px, gid) + jx, (double)lget(gs.py, gid) + jy));
     }
     if (act && hit) {
       Rng g; g.key = lget(gs.key, gid); g.ctr = off + Dm;
@@ -1058,9 +1009,7 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
       else s = e + direct_importance_parked<false, LEAN, RRT_OCC_TAG(LEAN, WAVES)>(*kp, g, cl, t, cn);
     }
     if (act) { lput(fr, t, s.r); lput(fg, t, s.g); lput(fb, t, s.b); }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
 
     RRT_ACC(t_shade, ts0);
     // ---- ordered fold by the group leader (raytrace_pixel's loop body, :136-158)
@@ -1094,10 +1043,7 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
       const uint32_t O = lget(gs.O, gid) + nh * Dh + ((uint32_t)n - nh) * Dm;
       const uint32_t hyp = n > 0 ? (uint32_t)((hm >> (n - 1)) & 1ull) : lget(gs.hyp, gid);
       bool st = i >= (int)kp->ns_aa;
-      if ((uint32_t)i % kp->samples_per_batch == 0) {  // ADAPTIVE == 1 (:147-158)
-        const double avg = s1 / i, sd = sqrt((s2 - avg * s1) / (i - 1));
-        if (1.96 * sd / sqrt((double)i) <= (double)kp->max_tolerance * avg) st = true;
-      }
+      if ((uint32_t)i % kp->samples_per_batch == 0 && adaptive_stop(*kp, s1, s2, i)) st = true;
       if (st) stop = 1;
       else if (kp->cont && (uint32_t)((int)kp->ns_aa - i) >= kp->cont_min_left &&
                cont_push(*kp, lget(gs.px, gid), lget(gs.py, gid), lget(gs.slot, gid), (uint32_t)i, O, ret, s1, s2))
@@ -1116,10 +1062,7 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
           }
         }
 #endif
-        const spec r = ret / (float)i;
-        kp->rgb[3 * slot] = r.r; kp->rgb[3 * slot + 1] = r.g; kp->rgb[3 * slot + 2] = r.b;
-        kp->count[slot] = i;
-        if (kp->draws) kp->draws[slot] = O;
+        write_pixel(*kp, slot, ret / (float)i, i, O);
       } else if (stop == 0) {
         lput(gs.rr, gid, ret.r); lput(gs.rg, gid, ret.g); lput(gs.rb, gid, ret.b);
         lput(gs.s1, gid, s1); lput(gs.s2, gid, s2);
@@ -1147,23 +1090,9 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
       if (lane == 0) atomicAdd(&rrt_prof[slot[i]], (unsigned long long)sm);
     }
   }
-  for (int k = 0; k < 12; ++k) {
-    for (int off2 = 32; off2 > 0; off2 >>= 1) {
-      const uint64_t o2 = __shfl_xor(v[k], off2);
-      v[k] = v[k] > o2 ? v[k] : o2;
-    }
-    if (lane == 0) atomicAdd(&rrt_prof[k < 8 ? k : k + 8], (unsigned long long)v[k]);
-  }
   uint32_t nb = gl == 0 ? prof_blocks : 0;
   for (int off2 = 32; off2 > 0; off2 >>= 1) nb += __shfl_xor(nb, off2);
-  if (lane == 0) {
-    atomicMin(&rrt_prof[8], (unsigned long long)w_start);
-    atomicMax(&rrt_prof[9], (unsigned long long)w_end);
-    const unsigned long long w = atomicAdd(&rrt_prof[10], 1ull) & 16383;
-    rrt_prof_ends[w] = w_end;
-    rrt_prof_starts[w] = w_start;
-    rrt_prof_work[w] = ((unsigned long long)nb << 32) | prof_samples;
-  }
+  prof_wave_record(v, lane, w_start, w_end, ((unsigned long long)nb << 32) | prof_samples);
 #endif
 }
 
@@ -1176,20 +1105,16 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
 // Claim index ix of the pass (a whole wave calls it together: ballots and one atomic per wave).
 __device__ __forceinline__ void pixel_pass_one(const KParams& kp, uint32_t ix, uint32_t lane) {
   using namespace rrt;
-  const uint32_t ts = kp.tile_size, tpix = ts * ts;
   bool listed = false, heavy = false;
   if (ix < kp.n_pixels) {
-    const uint32_t tl = kp.tile_order[ix / tpix], r = claim_r(ix % tpix, ts);
-    const uint32_t x = kp.tiles[2 * tl] + r % ts, y = kp.tiles[2 * tl + 1] + r / ts;
-    if (x >= kp.clip_x0 && y >= kp.clip_y0 && x < kp.clip_x1 && y < kp.clip_y1) {
-      if (pixel_miss_proof(kp, x, y)) {
-        const uint32_t slot = tl * tpix + r, n = min(kp.ns_aa, kp.samples_per_batch);
-        kp.rgb[3 * slot] = 0.0f; kp.rgb[3 * slot + 1] = 0.0f; kp.rgb[3 * slot + 2] = 0.0f;
-        kp.count[slot] = (int32_t)n;
-        if (kp.draws) kp.draws[slot] = n * kp.draws_miss;
+    const ClaimPixel c = claim_pixel(kp, ix);
+    // in_clip, restated: through the helper this pass spills two more SGPRs
+    if (c.x >= kp.clip_x0 && c.y >= kp.clip_y0 && c.x < kp.clip_x1 && c.y < kp.clip_y1) {
+      if (pixel_miss_proof(kp, c.x, c.y)) {
+        write_proven_pixel(kp, c.slot);
       } else {
         listed = true;
-        heavy = kp.heavy_list && pixel_heavy(kp, x, y);
+        heavy = kp.heavy_list && pixel_heavy(kp, c.x, c.y);
       }
     }
   }
@@ -1209,10 +1134,10 @@ __device__ __forceinline__ void pixel_pass_one(const KParams& kp, uint32_t ix, u
   // first hypothesis for the pixel)
   uint32_t hint = 0u;
   if (listed) {
-    const uint32_t tl = kp.tile_order[ix / tpix], r = claim_r(ix % tpix, ts);
-    const uint32_t x = kp.tiles[2 * tl] + r % ts, y = kp.tiles[2 * tl + 1] + r / ts;
+    // (decoded again, not kept across the ballots above)
+    const ClaimPixel c = claim_pixel(kp, ix);
     Counters cn = {};
-    hint = camera_miss_proof<false>(kp, ld3(kp.cam.pos), pixel_ray_dir(kp, x + 0.5, y + 0.5), cn) ? 0u : 1u;
+    hint = camera_miss_proof<false>(kp, ld3(kp.cam.pos), pixel_ray_dir(kp, c.x + 0.5, c.y + 0.5), cn) ? 0u : 1u;
   }
   const uint64_t b = __ballot(listed), lt = (1ull << lane) - 1ull;
   if (kp.claim_back) {
@@ -1256,18 +1181,12 @@ __global__ __launch_bounds__(256) void rrt_strip_proof_kernel(const KParams* __r
   const uint32_t s = blockIdx.x * 256u + threadIdx.x;
   const uint32_t ts = kp.tile_size, tpix = ts * ts;
   if (s < kp.n_pixels / 64u) {
-    const uint32_t ix0 = s * 64u, tl = kp.tile_order[ix0 / tpix], r0 = claim_r(ix0 % tpix, ts);
-    const uint32_t w = 8u, hh = 8u;
-    const uint32_t x = kp.tiles[2 * tl] + r0 % ts, y = kp.tiles[2 * tl + 1] + r0 / ts;
+    const uint32_t ix0 = s * 64u, w = 8u, hh = 8u;
+    const ClaimPixel c0 = claim_pixel(kp, ix0);  // the strip's first pixel: its top left corner
+    const uint32_t tl = c0.tl, x = c0.x, y = c0.y;
     const bool inside = x >= kp.clip_x0 && y >= kp.clip_y0 && x + w <= kp.clip_x1 && y + hh <= kp.clip_y1;
     if (inside && rect_miss_proof(kp, (double)x, (double)y, (double)w, (double)hh)) {
-      const uint32_t n = min(kp.ns_aa, kp.samples_per_batch);
-      for (uint32_t k = 0; k < 64u; ++k) {
-        const uint32_t slot = tl * tpix + claim_r(ix0 % tpix + k, ts);
-        kp.rgb[3 * slot] = 0.0f; kp.rgb[3 * slot + 1] = 0.0f; kp.rgb[3 * slot + 2] = 0.0f;
-        kp.count[slot] = (int32_t)n;
-        if (kp.draws) kp.draws[slot] = n * kp.draws_miss;
-      }
+      for (uint32_t k = 0; k < 64u; ++k) write_proven_pixel(kp, tl * tpix + claim_r(ix0 % tpix + k, ts));
       kp.strip_list[s] = 1u;
     } else {
       kp.strip_list[s] = 0u;
@@ -1300,19 +1219,16 @@ __global__ __launch_bounds__(256, WAVES) void rrt_first_kernel(const KParams* __
   for (uint32_t p = blockIdx.x * blockDim.x + t; p < kp.n_pixels; p += gridDim.x * blockDim.x) {
     const uint32_t tl = p / tpix, r = p % tpix, lx = r % ts, ly = r / ts;
     const uint32_t x = kp.tiles[2 * tl] + lx, y = kp.tiles[2 * tl + 1] + ly;
-    if (!(x >= kp.clip_x0 && y >= kp.clip_y0 && x < kp.clip_x1 && y < kp.clip_y1)) continue;
+    if (!in_clip(&kp, x, y)) continue;
     Rng g; g.key = rrt_pixel_key(kp.seed, x, y); g.ctr = 0;
     double jx, jy; g.grid(jx, jy);
     const double sx = (double)x + jx, sy = (double)y + jy;
-    const double cx = sx / kp.frame_w, cy = sy / kp.frame_h;  // Camera::generate_ray (:182-187)
-    const double vx = (1 - cx) * cam.blx + cx * -cam.blx, vy = (1 - cy) * cam.bly + cy * -cam.bly;
-    const v3 w = (smul(vx, ld3(cam.c2w0)) + smul(vy, ld3(cam.c2w1))) + smul(-1.0, ld3(cam.c2w2));
     Isect is;
-    const v3 wd = unit(w);
+    const v3 wd = pixel_ray_dir(kp, sx, sy);
     const bool hit = !camera_proven_miss<false, LEAN == V_KERR>(kp, ld3(cam.pos), wd, cn) &&
                      query<false, false, LEAN == V_KERR, is_lean(LEAN)>(kp, ld3(cam.pos), wd, &is, cn);
     spec s = S(0, 0, 0);
-    if (!hit && !is_lean(LEAN) && kp.env.w) s = env_dir(kp.env, unit(w));
+    if (!hit && !is_lean(LEAN) && kp.env.w) s = env_dir(kp.env, pixel_ray_dir(kp, sx, sy));
     if (hit) {
       park_hit(cl, t, is);
       g.ctr = kp.draws_miss;

@@ -94,7 +94,7 @@ def test_plan_layout():
 
 @pytest.mark.parametrize("world", [2, 3, 4, 5, 6, 7, 8])
 def test_tile_deal_matches_frame_plan(world):
-    """The library's block-cyclic deal (rrt_partition_tiles for bench.py's ranks, rrt_region_tiles
+    """The library's lattice deal (rrt_partition_tiles for bench.py's ranks, rrt_region_tiles
     for rrt_group_render's members) against rrt_frame.FramePlan, on the BASELINE frame sizes and a
     ragged region: every tile of the frame or region exactly once, tile (tx, ty) to rank
     (tx + S ty) % world with S = 1, 1, 1, 2, 1, 3, 3 for world 2..8 (the integer nearest 0.382 world
