@@ -203,6 +203,49 @@ int rrt_set_disk(rrt_ctx* ctx, const rrt_disk_desc* disk);
 /* 1 and the disk in force (r_in resolved against the current spacetime: 0 -> the ISCO radius in M
  * if the spacetime is Kerr), or 0 without a disk; works on a host-only context. */
 int rrt_get_disk(const rrt_ctx* ctx, rrt_disk_desc* out);
+/* Moving observer of a Kerr hole (build-defined).  Without one the camera hovers at rest
+ * and its coordinate axes are read as its rest frame.  With one the direction Camera::generate_ray
+ * yields is read in the rest frame of a camera that moves with `velocity` (in units of c; world
+ * components, read in the static observer's orthonormal triad at the camera position): the ray that is
+ * marched is its aberrated image in the static frame, carried into coordinates by that triad, and every
+ * camera sample is scaled once by the photon's energy in the camera's frame -- D_v = 1 / (gamma (1 -
+ * beta . n')) against the static observer, D = D_v / sqrt(1 - f) against infinity (f the Kerr-Schild
+ * metric's at the camera): the sky x D^4, the disk's colour rule at g D in place of g, a surface hit's
+ * whole sample x D_v^4 (surfaces stay at the camera's potential).  No RNG draw is added or removed.
+ * RRT_OBSERVER_FRAME_COORDINATE keeps the coordinate axes as the static frame (no triad, D = D_v);
+ * with a zero velocity it is the identity: every output is bit for bit what it is without an observer.
+ * Rendered by one build of the general per-pixel-loop kernel that takes the disk, the sky rule and the
+ * disk's colour rule at run time.  At render time RRT_E_INVALID for a Schwarzschild-kind spacetime (take
+ * RRT_METRIC_KERR with spin 0), for a camera at or inside the static limit (f >= 1; FRAME_STATIC), with
+ * RRT_RENDER_WAVEFRONT, RRT_RENDER_DEEP_SAMPLE, RRT_RENDER_COUNTERS or the reference's switch flags.
+ * The members of a group share the observer.  rrt_trace_camera applies it to the rays it generates (the
+ * records are rrt_trace_rays' for (cam.pos, d_eff); lane per ray only: RRT_TRACE_WAVE_PER_RAY is
+ * RRT_E_INVALID); rrt_trace_rays ignores it. */
+enum { RRT_OBSERVER_FRAME_STATIC = 0, RRT_OBSERVER_FRAME_COORDINATE = 1 };
+enum { RRT_OBSERVER_NO_BEAMING = 1u << 0 };  /* every factor 1: aberration alone */
+#define RRT_OBSERVER_MAX_SPEED 0.999
+typedef struct {
+  double velocity[3];         /* beta; |beta| <= RRT_OBSERVER_MAX_SPEED */
+  uint32_t frame;             /* RRT_OBSERVER_FRAME_* */
+  uint32_t flags;             /* RRT_OBSERVER_* */
+  uint32_t reserved[4];       /* 0 */
+} rrt_observer_desc;            /* 48 bytes */
+/* NULL removes the observer.  RRT_E_INVALID: a velocity that is not finite or faster than
+ * RRT_OBSERVER_MAX_SPEED, an unknown frame, unknown flags, non-zero reserved words.  A rejected
+ * descriptor leaves the observer in force. */
+int rrt_set_observer(rrt_ctx* ctx, const rrt_observer_desc* obs);
+/* 1 and the observer in force, or 0 without one; works on a host-only context.  resolved (may be NULL;
+ * filled only when a camera and a Kerr spacetime are set, as a launch would resolve them now):
+ * [0] f, [1] sg = sqrt(1 - f), [2] alpha = sg - 1, [3] D_g = 1 / sg, [4] ig = sqrt(1 - b2), [5] gamma,
+ * [6] kappa = gamma / (gamma + 1), [7..9] l in world axes, [10] b2 = beta . beta, [11] 1 if the observer
+ * is the identity, else 0.  FRAME_COORDINATE: alpha = 0, D_g = 1. */
+int rrt_get_observer(const rrt_ctx* ctx, rrt_observer_desc* out, double* resolved /* [12] */);
+/* The device's rule (rrt_device.h observer_ray) for the observer in force on n host directions n'
+ * (dirs [n][3], unit): the direction marched d_eff [n][3], D_v dv [n] and D dd [n]; the identity observer
+ * returns the directions untouched and ratios 1, as a render does.  RRT_OBSERVER_NO_BEAMING changes
+ * nothing here.  n == 0: RRT_OK without a launch.  Without an observer, or with one invalid for the camera
+ * and spacetime in force, the errors of a render launch; RRT_E_NO_DEVICE on a host-only context. */
+int rrt_observer_eval(rrt_ctx* ctx, const double* dirs, uint64_t n, double* d_eff, double* dv, double* dd);
 /* The validated envelope of the camera / pixel / shadow proofs (profiles/
  * r03_proof_sweep.json): delta_theta in [RRT_PROOF_DT_MIN, RRT_PROOF_DT_MAX] and r_s <=
  * RRT_PROOF_RS_OVER_EXTENT x the scene's largest root-box extent.  Outside it the kernels march

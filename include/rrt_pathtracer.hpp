@@ -68,6 +68,8 @@ class PathTracer {
   void set_lensed_sky(bool on);
   // the thin accretion disk of a Kerr hole (rrt_set_disk); nullptr removes it
   void set_disk(const rrt_disk_desc* disk);
+  // the moving observer of a Kerr hole (rrt_set_observer); nullptr removes it
+  void set_observer(const rrt_observer_desc* observer);
   void set_seed(uint64_t seed) { seed_ = seed; }  // keyed RNG seed
   void set_band_rows(size_t rows) { band_rows_ = rows; }  // rows per GPU submission (0: whole region)
 

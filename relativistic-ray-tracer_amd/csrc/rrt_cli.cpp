@@ -11,7 +11,9 @@
 // [--disk-no-redshift] (a thin accretion disk, radii in M, R_IN 0 = the ISCO; needs --kerr; DESIGN.md
 // §12) [--disk-temp KELVIN] [--disk-profile power|zero-torque|page-thorne] (the blackbody disk, DESIGN.md §13, §15;
 // without --disk-emission the emission is rrt_blackbody_tint of KELVIN) [--disk-light] (the disk
-// importance-sampled as a light).  The interactive viewer is out of scope: -f is
+// importance-sampled as a light) and --observer-velocity VX VY VZ [--observer-frame
+// static|coordinate] [--observer-no-beaming] (a moving camera: aberration and Doppler / gravitational
+// shift, needs --kerr).  The interactive viewer is out of scope: -f is
 // required.  Exit codes follow main.cpp (usage -> 1).
 #include <cstdio>
 #include <cstdlib>
@@ -48,6 +50,10 @@ static void usage(const char* binary) {
   std::printf("  --disk-profile <power|zero-torque|page-thorne>  Blackbody disk: T ~ r^-3/4, or the zero-torque or the\n"
               "                   Page-Thorne (spin-dependent) profile peaking at KELVIN\n");
   std::printf("  --disk-light     Sample the disk as a light under importance-sampled direct light; needs --disk\n");
+  std::printf("  --observer-velocity <VX> <VY> <VZ>  Moving camera: velocity in units of c (world axes, read in the static\n"
+              "                   observer's frame at the camera; |v| <= 0.999); needs --kerr\n");
+  std::printf("  --observer-frame <static|coordinate>  The frame the velocity is read in (default static)\n");
+  std::printf("  --observer-no-beaming  Aberration alone: no Doppler or gravitational factor\n");
   std::printf("  -h               Print this help message\n");
 }
 
@@ -68,6 +74,9 @@ int main(int argc, char** argv) {
   rrt_disk_desc disk;
   std::memset(&disk, 0, sizeof(disk));
   disk.emission[0] = disk.emission[1] = disk.emission[2] = 1.0f;
+  bool has_observer = false, has_observer_opt = false;
+  rrt_observer_desc observer;
+  std::memset(&observer, 0, sizeof(observer));
   auto need = [&](int i, int n) {
     if (i + n >= argc) { usage(argv[0]); std::exit(1); }
   };
@@ -137,6 +146,20 @@ int main(int argc, char** argv) {
     }
     else if (a == "--disk-no-redshift") { disk.flags |= RRT_DISK_NO_REDSHIFT; }
     else if (a == "--disk-light") { disk.flags |= RRT_DISK_LIGHT; disk_light = true; }
+    else if (a == "--observer-velocity") {
+      need(i, 3);
+      for (int k = 0; k < 3; ++k) observer.velocity[k] = std::atof(argv[++i]);
+      has_observer = true;
+    }
+    else if (a == "--observer-frame") {
+      need(i, 1);
+      const std::string v = argv[++i];
+      if (v == "static") observer.frame = RRT_OBSERVER_FRAME_STATIC;
+      else if (v == "coordinate") observer.frame = RRT_OBSERVER_FRAME_COORDINATE;
+      else { usage(argv[0]); return 1; }
+      has_observer_opt = true;
+    }
+    else if (a == "--observer-no-beaming") { observer.flags |= RRT_OBSERVER_NO_BEAMING; has_observer_opt = true; }
     else if (a == "--kerr") {
       need(i, 1);
       kerr_spin = std::atof(argv[++i]);
@@ -169,6 +192,15 @@ int main(int argc, char** argv) {
       std::fprintf(stderr, "[rrt_render] --disk-temp must lie in [1000, 1e6] K\n");
       return 1;
     }
+  }
+  if (has_observer_opt && !has_observer) {
+    std::fprintf(stderr, "[rrt_render] --observer-frame and --observer-no-beaming need --observer-velocity VX VY VZ\n");
+    return 1;
+  }
+  if (has_observer && kerr_spin < 0) {
+    std::fprintf(stderr, "[rrt_render] --observer-velocity needs --kerr A (the observer is built for the Kerr march; "
+                         "take --kerr 0 for a Schwarzschild hole)\n");
+    return 1;
   }
   if (!to_file) {
     std::fprintf(stderr, "[rrt_render] the interactive viewer is not part of this build: pass -f <file.png>\n");
@@ -219,6 +251,7 @@ int main(int argc, char** argv) {
   if (kerr_spin >= 0) pt.set_kerr(kerr_spin, kerr_axis);
   if (lensed_sky) pt.set_lensed_sky(true);
   if (has_disk) pt.set_disk(&disk);
+  if (has_observer) pt.set_observer(&observer);
   // Application::set_up_pathtracer (application.cpp:622-628)
   pt.set_camera(&camera);
   pt.set_scene(scene);

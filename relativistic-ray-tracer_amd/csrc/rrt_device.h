@@ -362,6 +362,11 @@ struct DiskRec {
   spec rgb;
   bool hit;
 };
+// ... and in the observer's build (kerr_march with RT) the crossing's radius (scene
+// units) and redshift besides: a camera ray's colour is re-evaluated at g x D (est_radiance)
+struct DiskRecRT : DiskRec {
+  double r, g;
+};
 
 // BVHAccel::intersect_micro (bvh.cpp:115-138) for one micro segment.  ANY: shadow query, stop
 // at the first accepted primitive (only the boolean is used; result-identical).
@@ -1071,7 +1076,7 @@ __device__ __forceinline__ void audit_note(const KParams& kp, int k, bool violat
   if (violated) atomicAdd(kp.audit + 2 * k + 1, 1ull);
 }
 __device__ __forceinline__ bool kerr_occluded_proof(const KParams& kp, v3 o, v3 d);
-template <bool ANY, bool COUNT, bool EXIT = false, bool DISK = false, bool BB = false, bool PT = false>
+template <bool ANY, bool COUNT, bool EXIT = false, bool DISK = false, bool BB = false, bool PT = false, bool RT = false>
 __device__ __forceinline__ bool kerr_march(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn, QRec* qr = nullptr,
                                            ExitRec* xr = nullptr, DiskRec* dk = nullptr);
 template <bool ANY, bool COUNT>
@@ -1199,6 +1204,38 @@ __device__ __forceinline__ spec disk_rgb(const DDisk& dd, double r, double g) {
   }
   return S(f[0], f[1], f[2]);
 }
+// disk_rgb with the colour rule of the disk in force taken at run time (the observer's build, DESIGN.md
+// §16): plain, blackbody, or blackbody with the Page-Thorne profile -- rrt_launch_disk's choice
+__device__ __forceinline__ spec disk_rgb_rt(const DDisk& dd, double r, double g) {
+  if (!dd.blackbody) return disk_rgb<false, false>(dd, r, g);
+  if (dd.profile == RRT_DISK_PROFILE_PAGE_THORNE) return disk_rgb<true, true>(dd, r, g);
+  return disk_rgb<true, false>(dd, r, g);
+}
+// The moving observer (rrt_set_observer).  np: the unit direction Camera::generate_ray
+// yields, read in the moving camera's rest frame.  The static-frame viewing direction n = the
+// aberration of np by the velocity beta (received light: the ray is marched as a photon leaving the
+// camera), then the static triad's leg along n in coordinates, k = n + alpha (l . n) l, whose unit
+// vector kerr_init turns into the photon's covector.  dv = E_camera / E_static = 1 / (gamma (1 -
+// beta . np)); dd = D_g dv, the photon's energy in the camera's frame for p_t = -1.  + - x / sqrt,
+// correctly rounded, in the order written (tests/observer_check.py restates it bit for bit).
+__device__ __forceinline__ v3 observer_ray(const DObs& ob, v3 np, double& dv, double& dd) {
+  const v3 b = ld3(ob.beta), lw = ld3(ob.lw);
+  const double s = (b.x * np.x + b.y * np.y) + b.z * np.z;
+  const double c = 1.0 - ob.kappa * s;
+  const double iden = xdiv(1.0, 1.0 - s);
+  const v3 n = V((np.x * ob.ig - b.x * c) * iden, (np.y * ob.ig - b.y * c) * iden, (np.z * ob.ig - b.z * c) * iden);
+  const double t = (lw.x * n.x + lw.y * n.y) + lw.z * n.z;
+  const double at = ob.alpha * t;
+  const v3 k = V(n.x + at * lw.x, n.y + at * lw.y, n.z + at * lw.z);
+  dv = ob.ig * iden;
+  dd = ob.dg * dv;
+  return unit(k);
+}
+// The beaming weight of an energy ratio x (bolometric radiance scales as x^4): (x x) (x x) as a float
+__device__ __forceinline__ float observer_w(double x) {
+  const double x2 = x * x;
+  return (float)(x2 * x2);
+}
 // The disk as a light (RRT_DISK_LIGHT): a point of the annulus drawn uniformly in the
 // coordinate area of the Kerr-Schild plane (x^2 + y^2 = r^2 + a^2: rho^2 uniform in rho_in2 ..
 // rho_in2 + rho_span), the flat direction wi from world point p to it and the flat solid-angle
@@ -1223,7 +1260,9 @@ __device__ __forceinline__ bool disk_sample(const DHole& h, const DDisk& dd, v3 
 // query: a capture wins; else the chord's closest primitive hit wins iff its
 // t <= t_disk = s max_t, else the disk (*dk; the Isect and qr->t as for a hit, bsdf and slot -1).
 // BB: dk->rgb is the blackbody colour; PT: with the Page-Thorne profile (§15).
-template <bool ANY, bool COUNT, bool EXIT, bool DISK, bool BB, bool PT>
+// RT (the observer's build): the colour rule is the disk's at run time (disk_rgb_rt), and
+// dk points at a DiskRecRT, which takes the crossing's radius and redshift too.
+template <bool ANY, bool COUNT, bool EXIT, bool DISK, bool BB, bool PT, bool RT>
 __device__ __forceinline__ bool kerr_march(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn, QRec* qr, ExitRec* xr,
                                            DiskRec* dk) {
   const DHole& h = kp.hole;
@@ -1287,7 +1326,15 @@ __device__ __forceinline__ bool kerr_march(const KParams& kp, v3 o, v3 d, Isect*
         if (prim && !(cross && q2->t > t_disk)) return true;
         if (cross) {
           double g;
-          const spec rgb = disk_radiance<BB, PT>(h, kp.disk, x, y, lz, g);
+          spec rgb;
+          if constexpr (RT) {
+            (void)disk_radiance<false, false>(h, kp.disk, x, y, lz, g);  // g alone
+            const double r = xsqrt((x * x + y * y) - h.a2);             // disk_radiance's r
+            rgb = disk_rgb_rt(kp.disk, r, g);
+            if (dk) { static_cast<DiskRecRT*>(dk)->r = r; static_cast<DiskRecRT*>(dk)->g = g; }
+          } else {
+            rgb = disk_radiance<BB, PT>(h, kp.disk, x, y, lz, g);
+          }
           if (dk) { dk->hit = true; dk->rgb = rgb; }
           const double gs = above ? g : -g;
           is->hit_p = a + vmul(sd, t_disk);
@@ -1554,14 +1601,15 @@ __device__ __forceinline__ bool shadow_occluded_proof(const KParams& kp, v3 o, v
 // row -- that row's capture test and walk, and every later row, are not run -- and *xr (if given)
 // says whether and where the ray escaped; Kerr: kerr_march's far march.
 // DISK (Kerr exit-mode builds): the march tests the accretion disk too (kerr_march; *dk); BB: its
-// colour is the blackbody rule's; PT: with the Page-Thorne profile
+// colour is the blackbody rule's; PT: with the Page-Thorne profile; RT: the colour rule at run time and
+// *dk a DiskRecRT (the observer's build)
 template <bool ANY, bool COUNT, bool KERR = false, bool W4 = true, bool EXIT = false, bool DISK = false, bool BB = false,
-          bool PT = false, bool SCOPED = false>
+          bool PT = false, bool SCOPED = false, bool RT = false>
 RRT_QUERY_ATTR bool query(const KParams& kp_in, v3 o, v3 d, Isect* is, Counters& cn, bool any_rt = false,
                           QRec* qr = nullptr, ExitRec* xr = nullptr, DiskRec* dk = nullptr) {
   // SCOPED: the march's constants (the hole, the root box, the grid) are read at the march's start
   const KParams& kp = kp_stage<SCOPED && !KERR>(kp_in);
-  if (KERR && EXIT) return kerr_march<ANY, COUNT, true, DISK, BB, PT>(kp, o, d, is, cn, qr, xr, dk);
+  if (KERR && EXIT) return kerr_march<ANY, COUNT, true, DISK, BB, PT, RT>(kp, o, d, is, cn, qr, xr, dk);
   if (KERR) return qr ? kerr_march<ANY, COUNT>(kp, o, d, is, cn, qr) : query_kerr<ANY, COUNT>(kp, o, d, is, cn);
   if (qr) qr->steps = (uint32_t)kp.hole.steps;  // all marched, unless a segment below ends the march
   if (COUNT && !kp.count_exec && !(kp.diag & 2)) cn.query++;

@@ -43,6 +43,9 @@ hipError_t rrt_launch_disk(const DDisk& disk, double m, uint64_t n, const double
 hipError_t rrt_launch_disk_sample(const DHole& hole, const DDisk& disk, uint64_t n, const double* p, const double* uv,
                                   double* wi, float* pdf, hipStream_t stream);
 hipError_t rrt_launch_trace_disk(const KParams* d_kp, const TraceArgs& a, int any, int exit, hipStream_t stream);
+hipError_t rrt_launch_trace_obs(const KParams* d_kp, const TraceArgs& a, int any, int exit, hipStream_t stream);
+hipError_t rrt_launch_observer(const DObs& obs, uint64_t n, const double* np, double* d_eff, double* dv, double* dd,
+                               hipStream_t stream);
 hipError_t rrt_launch_unpack(const uint32_t* tiles, uint32_t n_tiles, uint32_t ts, uint32_t fw, uint32_t fh,
                              const float* rgb_p, const int32_t* cnt_p, float* rgb, int32_t* cnt, hipStream_t stream);
 hipError_t rrt_launch_libm(int fn, uint64_t n, const double* a, const double* b, double* out, hipStream_t stream);
@@ -177,6 +180,8 @@ struct rrt_ctx {
   bool lensed_sky = false;  // RRT_SPACETIME_LENSED_SKY
   bool has_disk = false;    // rrt_set_disk; r_in == 0: the ISCO, resolved at launch
   rrt_disk_desc disk{};
+  bool has_obs = false;     // rrt_set_observer; its frame constants are resolved at launch
+  rrt_observer_desc obs{};
   // device scene
   DNode* d_nodes = nullptr;
   DPrimGeo* d_geo = nullptr;
@@ -1370,6 +1375,98 @@ static int check_disk(rrt_ctx* c) {
   return fill_disk_params(c, probe);
 }
 
+// ---------------------------------------------------------------- moving observer
+extern "C" int rrt_set_observer(rrt_ctx* c, const rrt_observer_desc* o) {
+  if (!c) return RRT_E_INVALID;
+  if (!o) { c->has_obs = false; c->obs = rrt_observer_desc{}; return RRT_OK; }
+  const double* b = o->velocity;
+  if (!(std::isfinite(b[0]) && std::isfinite(b[1]) && std::isfinite(b[2])))
+    return fail(c, RRT_E_INVALID, "observer velocity must be finite");
+  if (!((b[0] * b[0] + b[1] * b[1]) + b[2] * b[2] <= RRT_OBSERVER_MAX_SPEED * RRT_OBSERVER_MAX_SPEED))
+    return fail(c, RRT_E_INVALID, "observer speed must not exceed 0.999 c");
+  if (o->frame != RRT_OBSERVER_FRAME_STATIC && o->frame != RRT_OBSERVER_FRAME_COORDINATE)
+    return fail(c, RRT_E_INVALID, "unknown rrt_observer_desc frame");
+  if (o->flags & ~(uint32_t)RRT_OBSERVER_NO_BEAMING) return fail(c, RRT_E_INVALID, "unknown rrt_observer_desc flags");
+  for (uint32_t r : o->reserved)
+    if (r) return fail(c, RRT_E_INVALID, "rrt_observer_desc reserved words must be 0");
+  c->obs = *o;
+  c->has_obs = true;
+  return RRT_OK;
+}
+
+// The observer's constants for the camera and the Kerr hole h in force: kerr_fl's values at the camera
+// (rrt_device.h, IEEE arithmetic in its order), the static frame's and the velocity's.  res (may be
+// null): rrt_get_observer's resolved[12].
+static void resolve_observer(const rrt_observer_desc& o, const DCamera& cam, const DHole& h, DObs& d, double* res) {
+  const double v[3] = {cam.pos[0] - h.c[0], cam.pos[1] - h.c[1], cam.pos[2] - h.c[2]};
+  const double qx = v[0] * h.ex[0] + v[1] * h.ex[1] + v[2] * h.ex[2];  // kerr_local
+  const double qy = v[0] * h.ey[0] + v[1] * h.ey[1] + v[2] * h.ey[2];
+  const double qz = v[0] * h.ez[0] + v[1] * h.ez[1] + v[2] * h.ez[2];
+  const double zz = qz * qz;
+  const double w = ((qx * qx + qy * qy) + zz) - h.a2;
+  const double r2 = 0.5 * w + std::sqrt(0.25 * (w * w) + h.a2 * zz);
+  const double r = std::sqrt(r2);
+  const double iw = 1.0 / (r2 + h.a2);
+  const double l[3] = {(r * qx + h.a * qy) * iw, (r * qy - h.a * qx) * iw, qz / r};
+  const double f = ((2.0 * h.m) * (r * r2)) / (r2 * r2 + h.a2 * zz);
+  const bool coord = o.frame == RRT_OBSERVER_FRAME_COORDINATE;
+  const double sg = std::sqrt(1.0 - f);
+  d = DObs{};
+  for (int i = 0; i < 3; ++i) d.lw[i] = (h.ex[i] * l[0] + h.ey[i] * l[1]) + h.ez[i] * l[2];
+  d.alpha = coord ? 0.0 : sg - 1.0;
+  d.dg = coord ? 1.0 : 1.0 / sg;
+  const double* b = o.velocity;
+  for (int i = 0; i < 3; ++i) d.beta[i] = b[i];
+  const double b2 = (b[0] * b[0] + b[1] * b[1]) + b[2] * b[2];
+  d.ig = std::sqrt(1.0 - b2);
+  const double gamma = 1.0 / d.ig;
+  d.kappa = gamma / (gamma + 1.0);
+  d.on = 1u;
+  d.identity = (coord && b[0] == 0.0 && b[1] == 0.0 && b[2] == 0.0) ? 1u : 0u;
+  d.no_beaming = (o.flags & RRT_OBSERVER_NO_BEAMING) ? 1u : 0u;
+  if (res) {
+    res[0] = f; res[1] = sg; res[2] = d.alpha; res[3] = d.dg; res[4] = d.ig; res[5] = gamma; res[6] = d.kappa;
+    res[7] = d.lw[0]; res[8] = d.lw[1]; res[9] = d.lw[2]; res[10] = b2; res[11] = d.identity ? 1.0 : 0.0;
+  }
+}
+
+extern "C" int rrt_get_observer(const rrt_ctx* c, rrt_observer_desc* out, double* resolved) {
+  if (!c || !c->has_obs) return 0;
+  if (out) *out = c->obs;
+  if (resolved && c->has_camera && c->hole.kind == RRT_METRIC_KERR) {
+    DObs d;
+    resolve_observer(c->obs, c->cam, c->hole, d, resolved);
+  }
+  return 1;
+}
+
+// The observer of a render or trace launch: validated against the camera and the spacetime in force, its
+// constants resolved into kp.obs; the sky rule set for a launch without a disk (the observer's build
+// reads it from kp.disk.lensed).  Call with kp.cam and kp.hole filled.  Without an observer: RRT_OK, kp
+// untouched.
+static int fill_observer_params(rrt_ctx* c, KParams& kp) {
+  if (!c->has_obs) return RRT_OK;
+  if (c->hole.kind != RRT_METRIC_KERR)
+    return fail(c, RRT_E_INVALID, "the observer (rrt_set_observer) needs the Kerr march (the Schwarzschild stepper "
+                                  "carries no photon momentum): set RRT_METRIC_KERR with spin 0");
+  if (!c->has_camera) return fail(c, RRT_E_INVALID, "the observer (rrt_set_observer) needs a camera (rrt_set_camera)");
+  double res[12];
+  resolve_observer(c->obs, kp.cam, kp.hole, kp.obs, res);
+  if (c->obs.frame == RRT_OBSERVER_FRAME_STATIC && !(res[0] < 1.0))
+    return fail(c, RRT_E_INVALID, "the observer (rrt_set_observer) has no static frame: the camera lies at or inside "
+                                  "the static limit (f >= 1)");
+  kp.disk.lensed = c->lensed_sky ? 1u : 0u;
+  return RRT_OK;
+}
+// the observer against the camera and spacetime in force, with no launch at hand
+static int check_observer(rrt_ctx* c) {
+  if (!c->has_obs) return RRT_OK;
+  KParams probe{};
+  probe.hole = c->hole;
+  probe.cam = c->cam;
+  return fill_observer_params(c, probe);
+}
+
 extern "C" void rrt_kerr_frame(const double* axis, double* ex, double* ey, double* ez) {
   // ez = unit(axis); ex = unit(t x ez) with t the world axis least aligned with ez; ey = ez x ex
   const double n = std::sqrt(axis[0] * axis[0] + axis[1] * axis[1] + axis[2] * axis[2]);
@@ -1631,10 +1728,11 @@ struct LaunchMode {
   bool kerr, sw;     // the Kerr march; the reference's compile-time switches (RRT_RENDER_THIN_LENS .. RRT_RENDER_ILLUM_MASK)
   bool sky, disk;    // the lensed sky (RRT_SPACETIME_LENSED_SKY); the accretion disk (rrt_set_disk, §12)
   bool path_pool;    // RRT_RENDER_WAVEFRONT
+  bool obs;          // the moving observer (rrt_set_observer)
 };
 static LaunchMode launch_mode(const rrt_ctx* c, const rrt_render_params* p, bool has_counters) {
   return LaunchMode{p->max_ray_depth >= 2, (p->flags & RRT_RENDER_COUNTERS) && has_counters, c->hole.kind == RRT_METRIC_KERR,
-                    ((p->flags >> 22) & 63u) != 0, c->lensed_sky, c->has_disk, (p->flags & RRT_RENDER_WAVEFRONT) != 0};
+                    ((p->flags >> 22) & 63u) != 0, c->lensed_sky, c->has_disk, (p->flags & RRT_RENDER_WAVEFRONT) != 0, c->has_obs};
 }
 
 // Every refusal of a render launch, before any device work: no HIP call.  The order is part of the
@@ -1644,12 +1742,18 @@ static int check_launch(rrt_ctx* c, const rrt_render_params* p, const LaunchMode
   if (!c->has_scene) return fail(c, RRT_E_INVALID, "no scene (rrt_set_scene)");
   if (!c->has_camera) return fail(c, RRT_E_INVALID, "no camera (rrt_set_camera)");
   if (int rc = check_disk(c)) return rc;  // fill_disk_params' failures
+  if (int rc = check_observer(c)) return rc;  // fill_observer_params' failures
   if (c->device < 0) return fail(c, RRT_E_NO_DEVICE, "host-only context cannot render");
   if (p->frame_w == 0 || p->frame_h == 0) return fail(c, RRT_E_INVALID, "frame size is zero");
   if (p->samples_per_batch == 0) return fail(c, RRT_E_INVALID, "samples_per_batch must be > 0");
   if (p->max_ray_depth > RRT_MAX_DEPTH) return fail(c, RRT_E_INVALID, "max_ray_depth > 16 not supported");
   if (ts == 0 || ts % 8 != 0) return fail(c, RRT_E_INVALID, "tile_size must be a positive multiple of 8");
   if (n_tiles == 0) return kLaunchEmpty;
+  // the observer has one general per-pixel-loop build (rrt_kernel.hip V_KERR_OBS), as the sky and the disk below
+  if (m.obs && (m.sw || (p->flags & (RRT_RENDER_WAVEFRONT | RRT_RENDER_DEEP_SAMPLE | RRT_RENDER_COUNTERS))))
+    return fail(c, RRT_E_INVALID, "the observer (rrt_set_observer) renders in the per-pixel-loop kernel only: not with "
+                                  "RRT_RENDER_WAVEFRONT, RRT_RENDER_DEEP_SAMPLE, RRT_RENDER_COUNTERS or the reference's "
+                                  "switch flags");
   if (m.sw && m.kerr) return fail(c, RRT_E_INVALID, "the reference's switches (THIN_LENS, ADAPTIVE, ILLUM, ENV_HEMI, "
                                                     "MICROFACET_HEMI) are built for the Schwarzschild stepper only");
   if (m.sw && ((((p->flags >> 22) & 63u) >> 4) ^ 2u) == 3u && p->max_ray_depth == 0)
@@ -1677,6 +1781,7 @@ static int check_launch(rrt_ctx* c, const rrt_render_params* p, const LaunchMode
 // The kernel build of a launch.  LEAN builds when the scene allows them (no environment map,
 // importance-sampled direct light) and the launch is a plain depth <= 1 one.
 static int choose_variant(const rrt_ctx* c, const rrt_render_params* p, const LaunchMode& m, const DDisk& d) {
+  if (m.obs) return rrt::V_KERR_OBS;  // the identity observer too
   if (m.disk) {
     if (d.blackbody && d.profile == RRT_DISK_PROFILE_PAGE_THORNE)
       return d.light ? rrt::V_KERR_DISK_PT_LIGHT : rrt::V_KERR_DISK_PT;
@@ -1899,7 +2004,7 @@ static LaunchPlan plan_launch(const rrt_ctx* c, const rrt_render_params* p, cons
   // lensed sky and the disk.  RRT_RENDER_WAVEFRONT: the bounce paths in the path pool kernel
   // (rrt_path.hip: one ray per lane per round, the paths' integrator state between rays in LDS), an A/B
   // variant: m3 269 ms at 3 waves/SIMD vs 172 ms for the per-pixel loop.
-  const bool pixel_loop = !m.path_pool && ((m.deep && !pl.deep_sample) || (flags & RRT_RENDER_PIXEL_LOOP) || m.sw || m.sky || m.disk);
+  const bool pixel_loop = !m.path_pool && ((m.deep && !pl.deep_sample) || (flags & RRT_RENDER_PIXEL_LOOP) || m.sw || m.sky || m.disk || m.obs);
   // The walk-skipping diagnostics (RRT_RENDER_DIAG_NO_*) are compiled into the per-sample and per-pixel-loop
   // kernels only: the batch and heavy kernels' per-segment path does not carry their branch (rrt_device.h
   // segment_walk, SCOPED), so a launch that sets one takes the per-sample kernel.
@@ -2012,7 +2117,7 @@ static std::string kernel_name(const LaunchPlan& pl, const LaunchMode& m) {
       std::snprintf(name, sizeof(name), "%srrt_path_kernel<%d>", pass, (pl.waves >= 2 && pl.waves <= 4) ? pl.waves : RRT_PATH_WAVES);
       break;
     case Family::PixelLoop:
-      std::snprintf(name, sizeof(name), "%srrt_render_kernel<%s, %s, %d, ...>", pass, tf[m.deep || m.sw || m.sky || m.disk],
+      std::snprintf(name, sizeof(name), "%srrt_render_kernel<%s, %s, %d, ...>", pass, tf[m.deep || m.sw || m.sky || m.disk || m.obs],
                     tf[pl.count], pl.variant == rrt::V_LEAN_POINT ? rrt::V_GENERAL : pl.variant);
       break;
     case Family::PerSample:
@@ -2202,9 +2307,10 @@ static int launch(rrt_ctx* c, const rrt_render_params* p, const uint32_t* tiles,
   kp.sw = (p->flags >> 22) & 63u;  // the build V_SW (rrt_kernel.hip)
   kp.lens_r = c->lens_r; kp.focal = c->focal;
   if (int rc = fill_disk_params(c, kp)) return rc;  // (check_launch has passed check_disk)
+  if (int rc = fill_observer_params(c, kp)) return rc;  // (... and check_observer)
   // the switches' build marches every ray exactly; the lensed sky's and the disk's run no proof at all
   if (m.sw) { kp.miss.on = 0u; kp.occ.on = 0u; }
-  if (m.sky || m.disk) { kp.miss.on = 0u; kp.occ.on = 0u; kp.kproof.on = 0u; }
+  if (m.sky || m.disk || m.obs) { kp.miss.on = 0u; kp.occ.on = 0u; kp.kproof.on = 0u; }
   const LaunchPlan pl = plan_launch(c, p, m, proofs_valid, n_tiles, ts, kp);
   return enqueue(c, p, m, pl, kp, tiles, n_tiles, ts, stream);
 }
@@ -2343,6 +2449,36 @@ extern "C" int rrt_disk_sample(rrt_ctx* c, const double* p, const double* uv, ui
   return RRT_OK;
 }
 
+extern "C" int rrt_observer_eval(rrt_ctx* c, const double* dirs, uint64_t n, double* d_eff, double* dv, double* dd) {
+  if (!c || (n && (!dirs || !d_eff || !dv || !dd))) return fail(c, RRT_E_INVALID, "bad argument");
+  if (!c->has_obs) return fail(c, RRT_E_INVALID, "no observer (rrt_set_observer)");
+  KParams probe{};  // the observer's device constants as a launch fills them
+  probe.hole = c->hole;
+  probe.cam = c->cam;
+  if (int rc = fill_observer_params(c, probe)) return rc;
+  if (c->device < 0) return fail(c, RRT_E_NO_DEVICE, "no device");
+  if (n == 0) return RRT_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  double* di = nullptr;
+  double* de = nullptr;
+  double* dvv = nullptr;
+  double* ddd = nullptr;
+  struct Free {
+    void** p[4];
+    ~Free() { for (void** q : p) if (*q) (void)hipFree(*q); }
+  } guard{{(void**)&di, (void**)&de, (void**)&dvv, (void**)&ddd}};
+  HIPCHK(c, hipMalloc(&di, sizeof(double) * 3 * n));
+  HIPCHK(c, hipMalloc(&de, sizeof(double) * 3 * n));
+  HIPCHK(c, hipMalloc(&dvv, sizeof(double) * n));
+  HIPCHK(c, hipMalloc(&ddd, sizeof(double) * n));
+  HIPCHK(c, hipMemcpy(di, dirs, sizeof(double) * 3 * n, hipMemcpyHostToDevice));
+  HIPCHK(c, rrt_launch_observer(probe.obs, n, di, de, dvv, ddd, (hipStream_t)0));
+  HIPCHK(c, hipMemcpy(d_eff, de, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(dv, dvv, sizeof(double) * n, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(dd, ddd, sizeof(double) * n, hipMemcpyDeviceToHost));
+  return RRT_OK;
+}
+
 // ---------------------------------------------------------------- ray queries (rrt_query.hip)
 // One launch of the ray-query kernels: n caller rays (d_rays) or, with cam, the pixel-centre
 // camera rays of the region (x0, y0, w, n / w) of a fw x fh frame.  The context's workspace holds the
@@ -2359,6 +2495,13 @@ static int trace_launch(rrt_ctx* c, const rrt_trace_params* tp, bool cam, const 
   if (kerr && mode == RRT_TRACE_WAVE_PER_RAY)
     return fail(c, RRT_E_INVALID, "RRT_TRACE_WAVE_PER_RAY walks the Schwarzschild stepper's chain only (Kerr: lane per ray)");
   if (int rc = check_disk(c)) return rc;  // before any device work
+  // the observer bears on the rays the camera generates only: lane per ray, Kerr
+  const bool obs = cam && c->has_obs;
+  if (obs) {
+    if (int rc = check_observer(c)) return rc;
+    if (mode == RRT_TRACE_WAVE_PER_RAY)
+      return fail(c, RRT_E_INVALID, "with an observer (rrt_set_observer) rrt_trace_camera marches lane per ray only");
+  }
   if (c->device < 0) return fail(c, RRT_E_NO_DEVICE, "host-only context cannot trace");
   if (n == 0) return RRT_OK;
   if (!d_hits || (!cam && !d_rays)) return fail(c, RRT_E_INVALID, "null argument");
@@ -2371,12 +2514,18 @@ static int trace_launch(rrt_ctx* c, const rrt_trace_params* tp, bool cam, const 
   kp.frame_w = (double)fw; kp.frame_h = (double)fh;
   kp.frame_wi = fw; kp.frame_hi = fh;
   if (int rc = fill_disk_params(c, kp)) return rc;
+  if (obs)
+    if (int rc = fill_observer_params(c, kp)) return rc;
   HIPCHK(c, hipMemcpyAsync(c->d_kp, &kp, sizeof(KParams), hipMemcpyHostToDevice, stream));
   TraceArgs a{};
   a.rays = cam ? nullptr : reinterpret_cast<const double*>(d_rays);
   a.hits = d_hits;
   a.slot_prim = c->d_leaf;
   a.n = n; a.x0 = x0; a.y0 = y0; a.w = w ? w : 1u;
+  if (obs) {  // the observer's build (Kerr, lane per ray; the disk where kp.disk.on says so)
+    HIPCHK(c, rrt_launch_trace_obs(c->d_kp, a, (flags & RRT_TRACE_ANY_HIT) ? 1 : 0, (flags & RRT_TRACE_EXIT) ? 1 : 0, stream));
+    return RRT_OK;
+  }
   if (c->has_disk) {  // the disk builds (Kerr, lane per ray)
     HIPCHK(c, rrt_launch_trace_disk(c->d_kp, a, (flags & RRT_TRACE_ANY_HIT) ? 1 : 0, (flags & RRT_TRACE_EXIT) ? 1 : 0, stream));
     return RRT_OK;
@@ -2456,6 +2605,7 @@ extern "C" int rrt_render(rrt_ctx* c, const rrt_render_params* p, uint32_t x0, u
   if (w == 0 || h == 0) return RRT_OK;
   if ((uint64_t)x0 + w > p->frame_w || (uint64_t)y0 + h > p->frame_h) return fail(c, RRT_E_INVALID, "region outside frame");
   if (int rc = check_disk(c)) return rc;
+  if (int rc = check_observer(c)) return rc;
   if (c->device < 0) return fail(c, RRT_E_NO_DEVICE, "host-only context cannot render");
   if (cancel && *cancel) return fail(c, RRT_E_CANCELLED, "cancelled");
   HIPCHK(c, hipSetDevice(c->device));
@@ -2885,6 +3035,10 @@ extern "C" int rrt_group_render(rrt_group* g, const rrt_render_params* p, uint32
     if (g->ctx[i]->has_disk != g->ctx[0]->has_disk ||
         (g->ctx[0]->has_disk && std::memcmp(&g->ctx[i]->disk, &g->ctx[0]->disk, sizeof(rrt_disk_desc)) != 0))
       return group_fail(g, RRT_E_INVALID, "the members of a group must share the accretion disk (rrt_set_disk)");
+  for (uint32_t i = 1; i < n; ++i)  // ... and the observer
+    if (g->ctx[i]->has_obs != g->ctx[0]->has_obs ||
+        (g->ctx[0]->has_obs && std::memcmp(&g->ctx[i]->obs, &g->ctx[0]->obs, sizeof(rrt_observer_desc)) != 0))
+      return group_fail(g, RRT_E_INVALID, "the members of a group must share the observer (rrt_set_observer)");
   if (g->distinct && g->comm.empty())
     return group_fail(g, RRT_E_HIP, "the group's RCCL communicators were aborted after a failed gather");
   // the region's tiles, dealt over the members as a lattice (rrt_region_tiles)

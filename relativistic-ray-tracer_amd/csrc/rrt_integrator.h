@@ -5,6 +5,8 @@
 #pragma once
 #include "rrt_device.h"
 
+#include <type_traits>
+
 namespace rrt {
 
 // ------------------------------------------------------------------ integrator (part1_code.cpp)
@@ -19,8 +21,11 @@ template <bool ANY, bool COUNT, bool DEEP, int LEAN>
 __device__ __forceinline__ bool trace(const KParams& kp, v3 o, v3 d, Isect* is, Counters& cn, ExitRec* xr = nullptr,
                                       DiskRec* dk = nullptr) {
   return query<ANY, COUNT, is_kerr_build(LEAN), is_lean(LEAN), is_sky(LEAN) || is_disk(LEAN), is_disk(LEAN),
-               is_disk_bb(LEAN), is_disk_pt(LEAN)>(kp, o, d, is, cn, false, nullptr, xr, dk);
+               is_disk_bb(LEAN), is_disk_pt(LEAN), false, is_obs(LEAN)>(kp, o, d, is, cn, false, nullptr, xr, dk);
 }
+// the disk record of a build's marches: the observer's build (RT march) takes the crossing's r and g too
+template <int LEAN>
+using DiskRecOf = std::conditional_t<is_obs(LEAN), DiskRecRT, DiskRec>;
 // the emission a ray picks up at its hit: the hit primitive's BSDF's, or the disk's radiance
 __device__ __forceinline__ spec hit_emission(const KParams& kp, const Isect& is, const DiskRec& dk) {
   return dk.hit ? dk.rgb : emission(kp.bsdfs[is.bsdf]);
@@ -73,7 +78,7 @@ __device__ spec direct_hemisphere(const KParams& kp, Rng& g, const Isect& is, Co
     v3 wi_world = to_world(f, w_in);
     Isect is2;
     if (is_disk(LEAN)) {  // the emitter term takes the disk's radiance where the ray ends on the disk
-      DiskRec dk = {S(0, 0, 0), false};
+      DiskRecOf<LEAN> dk; dk.rgb = S(0, 0, 0); dk.hit = false;
       if (trace<false, COUNT, DEEP, LEAN>(kp, is.hit_p + smul(EPS_D, wi_world), wi_world, &is2, cn, nullptr, &dk))
         L = L + (hit_emission(kp, is2, dk) * bsdf_f(b, w_out, w_in)) * (float)w_in.z;
       continue;
@@ -104,7 +109,7 @@ __device__ __forceinline__ spec disk_direct(const KParams& kp, Rng& g, const Ise
     v3 w_in = to_local(f, wi_world);
     if (w_in.z < 0) continue;
     Isect is2;
-    DiskRec dk = {S(0, 0, 0), false};
+    DiskRecOf<LEAN> dk; dk.rgb = S(0, 0, 0); dk.hit = false;
     if (!trace<false, COUNT, DEEP, LEAN>(kp, is.hit_p + smul(EPS_D, wi_world), wi_world, &is2, cn, nullptr, &dk) || !dk.hit)
       continue;
     L = L + ((dk.rgb * bsdf_f<LEAN>(b, to_local(f, is.w_out), w_in)) * (float)w_in.z) / pdf;
@@ -210,7 +215,7 @@ __device__ __forceinline__ spec at_least_one_bounce(const KParams& kp, Rng& g, I
       v3 wi_world = to_world(f, w_in);
       Isect is2;
       if (is_disk(LEAN)) {  // a bounce ray that ends on the disk ends the path there
-        DiskRec dk = {S(0, 0, 0), false};
+        DiskRecOf<LEAN> dk; dk.rgb = S(0, 0, 0); dk.hit = false;
         if (trace<false, COUNT, true, LEAN>(kp, cur.hit_p + smul(EPS_D, wi_world), wi_world, &is2, cn, nullptr, &dk) &&
             k + 1 < LV::D) {
           lv.bounce(k, sample, (float)fabs(w_in.z), pdf, hit_emission(kp, is2, dk));

@@ -70,11 +70,17 @@ constexpr int V_KERR_DISK_BB_LIGHT = 10;
 // chain is no run-time branch in their parents.  Everywhere else they behave as their parents.
 constexpr int V_KERR_DISK_PT = 11;
 constexpr int V_KERR_DISK_PT_LIGHT = 12;
+// V_KERR_OBS: the moving observer's build (rrt_set_observer): the disk-light build with
+// everything else taken at run time -- the disk (kp.disk.on), the sky rule (kp.disk.lensed), the disk
+// light (kp.disk.light) and the colour rule (kp.disk.blackbody / profile) -- so that one build serves
+// every Kerr frame with an observer; its camera rays pass through observer_ray (rrt_device.h).
+constexpr int V_KERR_OBS = 13;
 __host__ __device__ constexpr bool is_lean(int v) { return v == V_LEAN || v == V_LEAN_POINT; }
 __host__ __device__ constexpr bool is_sky(int v) { return v == V_SKY || v == V_KERR_SKY; }
 __host__ __device__ constexpr bool is_disk_pt(int v) { return v == V_KERR_DISK_PT || v == V_KERR_DISK_PT_LIGHT; }
+__host__ __device__ constexpr bool is_obs(int v) { return v == V_KERR_OBS; }
 __host__ __device__ constexpr bool is_disk_light(int v) {
-  return v == V_KERR_DISK_LIGHT || v == V_KERR_DISK_BB_LIGHT || v == V_KERR_DISK_PT_LIGHT;
+  return v == V_KERR_DISK_LIGHT || v == V_KERR_DISK_BB_LIGHT || v == V_KERR_DISK_PT_LIGHT || is_obs(v);
 }
 __host__ __device__ constexpr bool is_disk_bb(int v) { return v == V_KERR_DISK_BB || v == V_KERR_DISK_BB_LIGHT || is_disk_pt(v); }
 __host__ __device__ constexpr bool is_disk(int v) { return v == V_KERR_DISK || is_disk_bb(v) || is_disk_light(v); }
@@ -278,6 +284,20 @@ struct DDisk {
   double pt_norm;         // 1 / S(x_peak): `temperature` is the peak temperature
 };
 
+// The moving observer (rrt_set_observer; rrt_device.h observer_ray): the static frame's
+// constants at the camera, resolved by the host at every launch, and the velocity's.
+struct DObs {
+  double lw[3];           // l of the Kerr-Schild metric at the camera, in world axes
+  double alpha;           // sqrt(1 - f) - 1 (RRT_OBSERVER_FRAME_COORDINATE: 0)
+  double dg;              // D_g = 1 / sqrt(1 - f) (RRT_OBSERVER_FRAME_COORDINATE: 1)
+  double beta[3];         // velocity, world components read in the static triad
+  double ig, kappa;       // sqrt(1 - b2); gamma / (gamma + 1)
+  uint32_t on;            // 1: an observer is set (rendered by V_KERR_OBS)
+  uint32_t identity;      // 1: FRAME_COORDINATE with beta = 0: the direction passes through, no factor
+  uint32_t no_beaming;    // RRT_OBSERVER_NO_BEAMING: every factor 1
+  uint32_t pad;
+};
+
 #define RRT_MAX_QUEUES 8
 #define RRT_QUEUE_STRIDE 16  // counters 64 B apart
 
@@ -414,7 +434,8 @@ struct KParams {
   uint32_t cont_ticks;    // a heavy block stops waiting after this long without work (wall clock)
   uint32_t cont_waiters;  // heavy blocks blockIdx < cont_waiters wait for continuations; the others
                           // leave once the heavy list is done (their slots go back to the batch kernel)
-  DDisk disk;             // the accretion disk (last: every earlier field keeps its offset)
+  DDisk disk;             // the accretion disk (every earlier field keeps its offset)
+  DObs obs;               // the moving observer (behind the disk: every earlier field keeps its offset)
 #if RRT_PROFILE
   // diagnostic build: per-wave progress records in host-coherent memory (RRT_WATCHDOG_MS), read by
   // the host while the kernels run: [wave][4] = {iteration, state, pixel, marker}; batch waves

@@ -14,10 +14,34 @@
 
 namespace rrt {
 
+// What observer_ray found for a camera sample of the observer's build (V_KERR_OBS): the
+// energy ratios E_camera / E_static and E_camera / E_infinity, and whether the factors apply at all
+// (not under the identity observer or RRT_OBSERVER_NO_BEAMING)
+struct ObsFac { double dv, dd; bool on; };
+
+// of: the observer's build only -- the sample's factors, each applied once: the sky x w(D), the disk's
+// colour rule at g x D, a surface hit's whole sample x w(D_v)
 template <bool DEEP, bool COUNT, int LEAN, int W = 0, class LV = LevelsPriv>
-__device__ __forceinline__ spec est_radiance(const KParams& kp, Rng& g, v3 o, v3 d, Counters& cn, LV lv = LV()) {  // :103-123
+__device__ __forceinline__ spec est_radiance(const KParams& kp, Rng& g, v3 o, v3 d, Counters& cn, LV lv = LV(),
+                                             const ObsFac* of = nullptr) {  // :103-123
   Isect is;
-  if (is_disk(LEAN)) {
+  if constexpr (is_obs(LEAN)) {
+    // the disk builds' rule below with every choice at run time, and the observer's factors
+    ExitRec xr = {V(0.0, 0.0, 0.0), false};
+    DiskRecOf<LEAN> dk; dk.rgb = S(0, 0, 0); dk.hit = false;
+    if (!trace<false, COUNT, DEEP, LEAN>(kp, o, d, &is, cn, kp.disk.lensed ? &xr : nullptr, &dk)) {
+      if (!kp.env.w) return S(0, 0, 0);
+      if (kp.disk.lensed && !xr.escaped) return S(0, 0, 0);
+      const spec sky = env_dir(kp.env, kp.disk.lensed ? xr.e : d);
+      return of->on ? sky * observer_w(of->dd) : sky;
+    }
+    if (dk.hit) return of->on ? disk_rgb_rt(kp.disk, dk.r, dk.g * of->dd) : dk.rgb;
+    const spec e = emission(kp.bsdfs[is.bsdf]);
+    spec L = e;
+    if (kp.max_ray_depth == 1) L = e + one_bounce<COUNT, LEAN, DEEP>(kp, g, is, cn);
+    else if (kp.max_ray_depth >= 2) L = e + at_least_one_bounce<COUNT, general_of(LEAN)>(kp, g, is, cn, lv);
+    return of->on ? L * observer_w(of->dv) : L;
+  } else if (is_disk(LEAN)) {
     // the disk build: a camera ray that reaches the disk returns its radiance; a miss takes the sky
     // rule in force -- the lensed sky's (the far march runs) or the reference's (it does not)
     ExitRec xr = {V(0.0, 0.0, 0.0), false};
@@ -80,7 +104,19 @@ __device__ __forceinline__ spec raytrace_pixel(const KParams& kp, uint32_t x, ui
     } else {
       // Camera::generate_ray (part1_code.cpp:182-187)
       v3 w = (smul(vx, ld3(cam.c2w0)) + smul(vy, ld3(cam.c2w1))) + smul(-1.0, ld3(cam.c2w2));
-      s = est_radiance<DEEP, COUNT, LEAN, W>(kp, g, ld3(cam.pos), unit(w), cn, lv);
+      if constexpr (is_obs(LEAN)) {
+        // the moving observer: the generated direction is the camera's rest frame's; the
+        // identity observer (a launch constant: a wave-uniform branch) passes it through untouched
+        v3 dn = unit(w);
+        ObsFac of = {1.0, 1.0, false};
+        if (!kp.obs.identity) {
+          dn = observer_ray(kp.obs, dn, of.dv, of.dd);
+          of.on = !kp.obs.no_beaming;
+        }
+        s = est_radiance<DEEP, COUNT, LEAN, W>(kp, g, ld3(cam.pos), dn, cn, lv, &of);
+      } else {
+        s = est_radiance<DEEP, COUNT, LEAN, W>(kp, g, ld3(cam.pos), unit(w), cn, lv);
+      }
     }
     ret = ret + s;
     if (LEAN == V_SW && (kp.sw & SW_NO_ADAPTIVE)) { n = i + 1; continue; }  // ADAPTIVE 0
@@ -261,6 +297,19 @@ __global__ void rrt_disk_sample_kernel(const DHole hole, const DDisk disk, uint6
   }
 }
 
+// The moving observer's rule as the render kernel evaluates it (rrt_device.h observer_ray)
+// on n caller directions np [n][3]: rrt_observer_eval, the checker's handle.  The identity observer
+// passes the direction through with both ratios 1, as raytrace_pixel does.
+__global__ void rrt_observer_kernel(const DObs obs, uint64_t n, const double* np, double* d_eff, double* dv, double* dd) {
+  for (uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; k < n; k += (uint64_t)gridDim.x * blockDim.x) {
+    rrt::v3 d = rrt::V(np[3 * k], np[3 * k + 1], np[3 * k + 2]);
+    double v = 1.0, w = 1.0;
+    if (!obs.identity) d = rrt::observer_ray(obs, d, v, w);
+    d_eff[3 * k] = d.x; d_eff[3 * k + 1] = d.y; d_eff[3 * k + 2] = d.z;
+    dv[k] = v; dd[k] = w;
+  }
+}
+
 // ------------------------------------------------------------------ launch shims (C++ linkage)
 // Kernel selection: deep / counting variants are built once (1 wave per SIMD budget); the
 // depth <= 1 path has general and LEAN builds at 1..4 waves per SIMD (A/B knob `waves`).
@@ -280,6 +329,7 @@ hipError_t rrt_launch_render(const KParams& kp, const KParams* d_kp, int deep, i
     RRT_SKY_DISK(V_KERR_DISK) RRT_SKY_DISK(V_KERR_DISK_BB)
     RRT_SKY_DISK(V_KERR_DISK_LIGHT) RRT_SKY_DISK(V_KERR_DISK_BB_LIGHT)
     RRT_SKY_DISK(V_KERR_DISK_PT) RRT_SKY_DISK(V_KERR_DISK_PT_LIGHT)
+    RRT_SKY_DISK(V_KERR_OBS)  // the moving observer's build
 #undef RRT_SKY_DISK
     default: break;
   }
@@ -365,6 +415,14 @@ hipError_t rrt_launch_disk_sample(const DHole& hole, const DDisk& disk, uint64_t
   if (grid > 8192) grid = 8192;
   if (grid == 0) grid = 1;
   hipLaunchKernelGGL(rrt_disk_sample_kernel, dim3((uint32_t)grid), dim3(256), 0, stream, hole, disk, n, p, uv, wi, pdf);
+  return hipGetLastError();
+}
+hipError_t rrt_launch_observer(const DObs& obs, uint64_t n, const double* np, double* d_eff, double* dv, double* dd,
+                               hipStream_t stream) {
+  uint64_t grid = (n + 255) / 256;
+  if (grid > 8192) grid = 8192;
+  if (grid == 0) grid = 1;
+  hipLaunchKernelGGL(rrt_observer_kernel, dim3((uint32_t)grid), dim3(256), 0, stream, obs, n, np, d_eff, dv, dd);
   return hipGetLastError();
 }
 hipError_t rrt_launch_tonemap(uint32_t n, const float* rgb, uint32_t* out, float exposure, float inv_gamma,

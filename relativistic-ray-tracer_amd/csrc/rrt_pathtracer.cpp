@@ -232,6 +232,11 @@ void PathTracer::set_disk(const rrt_disk_desc* disk) {
     if (rrt_set_disk(c, disk) != RRT_OK) err_ = rrt_last_error(c);
 }
 
+void PathTracer::set_observer(const rrt_observer_desc* observer) {
+  for (rrt_ctx* c : ctxs_)
+    if (rrt_set_observer(c, observer) != RRT_OK) err_ = rrt_last_error(c);
+}
+
 rrt_render_params PathTracer::params() const {
   rrt_render_params p;
   rrt_render_params_default(&p);

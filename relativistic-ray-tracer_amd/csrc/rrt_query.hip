@@ -258,6 +258,60 @@ __global__ __launch_bounds__(256) void rrt_trace_disk_lane_kernel(const KParams*
   }
 }
 
+// ------------------------------------------------------------------ moving observer (rrt_set_observer)
+// A build of its own once more: the camera rays of rrt_trace_camera with an observer set,
+// each passed through observer_ray before the march.  The march is rrt_trace_disk_lane_kernel's, the disk
+// tested where kp.disk.on says so, and so is the record: pure geometry, what rrt_trace_rays returns for
+// (cam.pos, d_eff).
+template <bool EXIT, bool ANY>
+__global__ __launch_bounds__(256) void rrt_trace_obs_lane_kernel(const KParams* __restrict__ kpp, const TraceArgs a) {
+  using namespace rrt;
+  const KParams& kp = *kpp;
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= a.n) return;
+  v3 o, d;
+  load_ray<true>(kp, a, i, o, d);
+  if (!kp.obs.identity) {
+    double dv, dd;
+    d = observer_ray(kp.obs, d, dv, dd);
+  }
+  Isect is;
+  QRec qr = {-1, 0.0, 0u, false};
+  ExitRec xr = {V(0.0, 0.0, 0.0), false};
+  DiskRec dk = {S(0, 0, 0), false};
+  Counters cn = {};
+  const bool hit = kerr_march<ANY, false, EXIT, true>(kp, o, d, &is, cn, &qr, &xr, &dk);
+  if (hit && dk.hit) {
+    double2* h = reinterpret_cast<double2*>(a.hits) + 6 * (size_t)i;
+    const double2 z = make_double2(0.0, 0.0);
+    if (ANY) {
+      h[0] = z; h[1] = z; h[2] = z; h[3] = z; h[4] = z;
+    } else {
+      h[0] = make_double2(is.hit_p.x, is.hit_p.y);
+      h[1] = make_double2(is.hit_p.z, is.n.x);
+      h[2] = make_double2(is.n.y, is.n.z);
+      h[3] = make_double2(is.w_out.x, is.w_out.y);
+      h[4] = make_double2(is.w_out.z, qr.t);
+    }
+    uint4 tail;
+    tail.x = RRT_RAY_DISK; tail.y = 0xffffffffu; tail.z = 0xffffffffu; tail.w = qr.steps;
+    *reinterpret_cast<uint4*>(h + 5) = tail;
+  } else if (hit || qr.captured || !EXIT) {
+    store_hit(a, i, hit ? RRT_RAY_HIT : qr.captured ? RRT_RAY_CAPTURED : RRT_RAY_MISS, qr.steps, hit && !ANY, is, qr);
+  } else {
+    store_exit(a, i, qr.steps, xr);
+  }
+}
+// its launch: camera rays only (a.rays is null)
+hipError_t rrt_launch_trace_obs(const KParams* d_kp, const TraceArgs& a, int any, int exit, hipStream_t stream) {
+  const uint32_t grid = (a.n - 1u) / 256u + 1u;  // n > 0
+#define RRT_GO_O(X, A) hipLaunchKernelGGL((rrt_trace_obs_lane_kernel<X, A>), dim3(grid), dim3(256), 0, stream, d_kp, a)
+  if (exit) { if (any) RRT_GO_O(true, true); else RRT_GO_O(true, false); }
+  else      { if (any) RRT_GO_O(false, true); else RRT_GO_O(false, false); }
+#undef RRT_GO_O
+  return hipGetLastError();
+}
+
 // the disk kernels' launch: Kerr, lane per ray
 hipError_t rrt_launch_trace_disk(const KParams* d_kp, const TraceArgs& a, int any, int exit, hipStream_t stream) {
   const bool cam = a.rays == nullptr;

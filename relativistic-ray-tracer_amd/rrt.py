@@ -100,6 +100,16 @@ class DiskDesc(C.Structure):  # rrt_disk_desc
                 ("temperature", C.c_float), ("profile", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+RRT_OBSERVER_FRAME_STATIC, RRT_OBSERVER_FRAME_COORDINATE = 0, 1  # rrt_observer_desc.frame
+RRT_OBSERVER_NO_BEAMING = 1  # rrt_observer_desc.flags: every factor 1, aberration alone
+OBSERVER_FRAMES = {"static": RRT_OBSERVER_FRAME_STATIC, "coordinate": RRT_OBSERVER_FRAME_COORDINATE}
+OBSERVER_RESOLVED = ("f", "sg", "alpha", "D_g", "ig", "gamma", "kappa", "l_w", "b2", "identity")
+
+
+class ObserverDesc(C.Structure):  # rrt_observer_desc
+    _fields_ = [("velocity", C.c_double * 3), ("frame", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+
 class RenderParams(C.Structure):
     _fields_ = [("ns_aa", C.c_uint32), ("max_ray_depth", C.c_uint32), ("ns_area_light", C.c_uint32),
                 ("samples_per_batch", C.c_uint32), ("max_tolerance", C.c_float),
@@ -151,7 +161,7 @@ EXPORTS = ["rrt_abi_version", "rrt_create", "rrt_destroy", "rrt_last_error", "rr
            "rrt_set_proof_audit", "rrt_get_proof_audit", "rrt_get_search_tree4", "rrt_trace_rays",
            "rrt_trace_rays_device", "rrt_trace_camera", "rrt_trace_camera_device", "rrt_env_eval", "rrt_set_disk",
            "rrt_get_disk", "rrt_disk_eval", "rrt_blackbody_tint", "rrt_disk_sample",
-           "rrt_plan_prove_first"]
+           "rrt_plan_prove_first", "rrt_set_observer", "rrt_get_observer", "rrt_observer_eval"]
 AUDIT_KINDS = ("camera", "shadow", "pixel", "strip", "kerr", "zero")  # include/rrt.h RRT_AUDIT_*
 
 _lib = None
@@ -214,6 +224,10 @@ def lib():
             L.rrt_blackbody_tint.argtypes = [C.c_double, C.POINTER(C.c_float * 3)]
         if hasattr(L, "rrt_disk_sample"):  # absent from older builds loaded through RRT_LIB
             L.rrt_disk_sample.argtypes = [vp, vp, vp, C.c_uint64, vp, vp]
+        if hasattr(L, "rrt_set_observer"):  # absent from older builds loaded through RRT_LIB
+            L.rrt_set_observer.argtypes = [vp, C.POINTER(ObserverDesc)]
+            L.rrt_get_observer.argtypes = [vp, C.POINTER(ObserverDesc), vp]
+            L.rrt_observer_eval.argtypes = [vp, vp, C.c_uint64, vp, vp, vp]
         if hasattr(L, "rrt_set_proof_audit"):  # absent from older builds loaded through RRT_LIB
             L.rrt_set_proof_audit.argtypes = [vp, C.c_int]
             L.rrt_get_proof_audit.argtypes = [vp, vp]
@@ -552,6 +566,47 @@ class Renderer:
         out = np.zeros((len(r_m), 3), np.float32)
         self._chk(lib().rrt_disk_eval(self.h, _p(r_m), _p(g), len(r_m), _p(out)))
         return out
+
+    def set_observer(self, velocity=None, frame="static", beaming=True):
+        """The moving observer of a Kerr hole (rrt_set_observer): the camera moves with
+        `velocity` (beta, in units of c; world components read in the static observer's triad at the
+        camera), so its rays are aberrated and every camera sample is scaled by the photon's energy in
+        its frame.  frame="coordinate" reads the coordinate axes as the static frame (with a zero
+        velocity: the identity, bit for bit the render without an observer).  beaming=False
+        (RRT_OBSERVER_NO_BEAMING): aberration alone.  set_observer(None) removes it."""
+        if velocity is None:
+            self._chk(lib().rrt_set_observer(self.h, None))
+            return
+        d = ObserverDesc()
+        d.velocity[0], d.velocity[1], d.velocity[2] = (float(v) for v in velocity)
+        d.frame = OBSERVER_FRAMES[frame] if isinstance(frame, str) else frame
+        d.flags = 0 if beaming else RRT_OBSERVER_NO_BEAMING
+        self._chk(lib().rrt_set_observer(self.h, C.byref(d)))
+
+    def get_observer(self):
+        """The observer in force as a dict ("velocity", "frame", "beaming") or None.  With a camera and a
+        Kerr spacetime set, "resolved" holds the constants a launch would resolve now (OBSERVER_RESOLVED:
+        f, sg, alpha, D_g, ig, gamma, kappa, l_w (3), b2, identity)."""
+        d = ObserverDesc()
+        res = np.full(12, np.nan, np.float64)
+        if not lib().rrt_get_observer(self.h, C.byref(d), _p(res)):
+            return None
+        out = {"velocity": tuple(d.velocity), "frame": {v: k for k, v in OBSERVER_FRAMES.items()}[d.frame],
+               "beaming": not (d.flags & RRT_OBSERVER_NO_BEAMING)}
+        if not np.isnan(res[11]):
+            out["resolved"] = {"f": res[0], "sg": res[1], "alpha": res[2], "D_g": res[3], "ig": res[4], "gamma": res[5],
+                               "kappa": res[6], "l_w": res[7:10].copy(), "b2": res[10], "identity": bool(res[11])}
+        return out
+
+    def observer_eval(self, dirs):
+        """The device's observer rule (rrt_observer_eval) on the unit directions dirs [n, 3]
+        of the moving camera's rest frame: (d_eff float64 [n, 3], D_v float64 [n], D float64 [n])."""
+        dirs = np.ascontiguousarray(np.asarray(dirs, np.float64).reshape(-1, 3))
+        d_eff = np.zeros((len(dirs), 3), np.float64)
+        dv = np.zeros(len(dirs), np.float64)
+        dd = np.zeros(len(dirs), np.float64)
+        self._chk(lib().rrt_observer_eval(self.h, _p(dirs), len(dirs), _p(d_eff), _p(dv), _p(dd)))
+        return d_eff, dv, dd
 
     def libm_eval(self, fn, a, b=None):
         """The device's restated host-libm function `fn` (rrt_glibm.h) on float64 arrays a (, b)."""
