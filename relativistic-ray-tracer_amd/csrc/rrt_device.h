@@ -200,6 +200,7 @@ struct Counters {
   uint32_t bbox, micro, prim, query;
 #if RRT_PROFILE
   uint64_t t_micro, t_trav, t_query, t_proof, t_squery, t_strav;
+  uint64_t t_sproof;  // the shadow rays' occlusion proof: its part of t_squery
   uint64_t t_claim, t_chain, t_shade, t_fold;  // batch kernel phases
 #endif
 };
@@ -1386,10 +1387,15 @@ __device__ __forceinline__ bool occ_face(const DShadowProof& sp, int f, v3 a, v3
   return false;
 }
 // The segment a -> b with an end outside the trigger box: 1 = a certain crossing of a triangle of
-// a face that an end is past; -1 = no proof and b has left the root box (the ray leaves the room:
-// give up); 0 = go on.  Loops kept rolled: this runs once or twice per shadow ray.
+// a face that an end is past; -1 = no proof, b has left the root box and the launch gives up there
+// (kp.shadow_reentry == 0, A/B); 0 = go on.  With the re-entry rule (the default) a ray that has left
+// the room goes on too: a ray thrown out past the hole turns round within a few rows (v changes sign,
+// as in the reference's own recurrence) and its next chord crosses a wall from outside; occ_face takes
+// either direction, and a chord that comes back through a face without triangles continues inside.
+// Loops kept rolled: this runs once or twice per shadow ray, and once per row outside the room.
 __device__ __forceinline__ int occ_exit(const KParams& kp, v3 a, v3 b, double m) {
   const DShadowProof& sp = kp.occ;
+  // (a segment wholly outside the room meets no kept triangle: occ_face's plane test rejects it)
   bool out = false;
 #pragma unroll 1
   for (int f = 0; f < 6; ++f) {
@@ -1399,7 +1405,7 @@ __device__ __forceinline__ int occ_exit(const KParams& kp, v3 a, v3 b, double m)
     if (past && occ_face(sp, f, a, b, m)) return 1;
     out = out || !(f < 3 ? bk >= kp.miss.lo[k] : bk <= kp.miss.hi[k]);  // NaN: out
   }
-  return out ? -1 : 0;
+  return out && !kp.shadow_reentry ? -1 : 0;
 }
 // occ_exit out of line, one copy per kernel build W (inline or the whole proof out of
 // line measured slower)
@@ -2089,6 +2095,7 @@ __device__ __forceinline__ bool query_nx(const KParams& kp, v3 o, v3 d, Isect* i
     const KParams& kq = kp_stage<SCOPED>(kp);  // the proof's constants: live inside it only
     const bool occluded = shadow_occluded_proof<W>(kq, o, d, kq.hole.steps);
     RRT_ACC(t_squery, tp0);
+    RRT_ACC(t_sproof, tp0);
     if (occluded) {
       if (COUNT && kp.audit && audit_pick(kp, o, d)) {
         Counters c2 = {};

@@ -1627,8 +1627,9 @@ static void fill_scene_params(const rrt_ctx* c, uint32_t flags, KParams& kp) {
 
 // The constants of the three proofs (camera-ray miss, shadow-ray occlusion, Kerr occlusion) and each
 // one's switch.  Call with kp.hole filled (fill_scene_params).  Returns whether the launch lies in the
-// envelope the Schwarzschild proofs (and the pixel miss proof pass) hold in.
-static bool fill_proof_params(const rrt_ctx* c, uint32_t flags, KParams& kp) {
+// envelope the Schwarzschild proofs (and the pixel miss proof pass) hold in.  shadow_reentry: the
+// shadow proof's re-entry rule, from the launch's A/B knobs (plan_shadow_reentry).
+static bool fill_proof_params(const rrt_ctx* c, uint32_t flags, uint32_t shadow_reentry, KParams& kp) {
   bool proofs_valid = false;
   {  // camera-ray miss proof constants (rrt_device.h camera_miss_proof)
     const DHole& h = kp.hole;
@@ -1677,6 +1678,8 @@ static bool fill_proof_params(const rrt_ctx* c, uint32_t flags, KParams& kp) {
     // the point-light scenes' builds carry no proof (rrt_sample.hip RRT_OCC_TAG); off for them in
     // every kernel, so the counting passes count what their batch kernel executes
     kp.occ.on = (proofs_valid && any && fin && c->lean != 2 && !(flags & RRT_RENDER_NO_SHADOW_PROOF)) ? 1u : 0u;
+    // a ray that has left the root box goes on with the proof (rrt_device.h occ_exit); 0 (A/B): it gives up
+    kp.shadow_reentry = shadow_reentry;
     // Kerr shadow rays (rrt_device.h kerr_occluded_proof): the same face triangles
     // against a coarse march, inside the envelope its margin was swept over
     // (tools/kerr_proof_sweep.py -> profiles/r04_kerr_proof_sweep.json)
@@ -1833,6 +1836,7 @@ struct AbKnobs {
   const char *cont, *cont_min, *cont_room, *cont_waiters, *prio_ticks;  // RRT_AB_CONT .. RRT_AB_PRIO_TICKS
   const char* prove_first;  // RRT_AB_PROVE_FIRST
   const char* no_halfspace;  // RRT_AB_NO_HALFSPACE
+  const char* no_shadow_reentry;  // RRT_AB_NO_SHADOW_REENTRY
   static uint32_t u32(const char* s, uint32_t dflt) { return s ? (uint32_t)std::strtoul(s, nullptr, 10) : dflt; }
 };
 // The camera miss proof gate's launch constant (KParams::prove_first): 0, the default: the LEAN
@@ -1843,12 +1847,17 @@ static uint32_t plan_prove_first(const AbKnobs& ab) { return AbKnobs::u32(ab.pro
 // before the widened slab test; A/B: RRT_AB_NO_HALFSPACE=1 (any non-zero number): the slab test alone.  The
 // frames are the same bits either way: the rule only moves pixels from the batch kernel to the pass.
 static uint32_t plan_halfspace(const AbKnobs& ab) { return AbKnobs::u32(ab.no_halfspace, 0u) ? 0u : 1u; }
+// The shadow proof's re-entry rule (KParams::shadow_reentry): 1, the default: a shadow ray whose
+// segment end has left the root box goes on with the proof; A/B: RRT_AB_NO_SHADOW_REENTRY=1 (any non-zero
+// number): the proof gives up there and the ray is marched exactly.  The frames are the same bits either way: a
+// proven ray is one the exact march finds occluded.
+static uint32_t plan_shadow_reentry(const AbKnobs& ab) { return AbKnobs::u32(ab.no_shadow_reentry, 0u) ? 0u : 1u; }
 static AbKnobs read_ab_knobs(uint32_t v) {
   return AbKnobs{v & 0xffu, (v >> 8) & 0xfu, (v >> 12) & 0xfu, (v >> 16) & 0xfu, (v >> 20) & 3u, ((v >> 22) & 1u) != 0,
                  ((v >> 23) & 1u) != 0, (v >> 24) & 0xfu, (v >> 28) & 0xfu, std::getenv("RRT_AB_CONT"),
                  std::getenv("RRT_AB_CONT_MIN"), std::getenv("RRT_AB_CONT_ROOM"), std::getenv("RRT_AB_CONT_WAITERS"),
                  std::getenv("RRT_AB_PRIO_TICKS"), std::getenv("RRT_AB_PROVE_FIRST"),
-                 std::getenv("RRT_AB_NO_HALFSPACE")};
+                 std::getenv("RRT_AB_NO_HALFSPACE"), std::getenv("RRT_AB_NO_SHADOW_REENTRY")};
 }
 
 // the RNG draws of one camera sample that hits, at depth <= 1: jitter + the direct-lighting samplers
@@ -2290,7 +2299,7 @@ static int launch(rrt_ctx* c, const rrt_render_params* p, const uint32_t* tiles,
   if (int rc = check_launch(c, p, m, n_tiles, ts)) return rc == kLaunchEmpty ? RRT_OK : rc;
   KParams kp{};
   fill_scene_params(c, p->flags, kp);
-  const bool proofs_valid = fill_proof_params(c, p->flags, kp);
+  const bool proofs_valid = fill_proof_params(c, p->flags, plan_shadow_reentry(read_ab_knobs(p->variant)), kp);
   // the launch's own constants: the render settings, the frame, the tile list's shape and the outputs
   kp.ns_aa = p->ns_aa; kp.max_ray_depth = p->max_ray_depth; kp.ns_area_light = p->ns_area_light;
   kp.samples_per_batch = p->samples_per_batch; kp.max_tolerance = p->max_tolerance;

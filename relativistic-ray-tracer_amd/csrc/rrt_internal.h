@@ -436,6 +436,11 @@ struct KParams {
                           // leave once the heavy list is done (their slots go back to the batch kernel)
   DDisk disk;             // the accretion disk (every earlier field keeps its offset)
   DObs obs;               // the moving observer (behind the disk: every earlier field keeps its offset)
+  // shadow-ray occlusion proof (rrt_device.h occ_exit): 1: a ray whose segment end has left
+  // the root box without a certain crossing goes on (it may turn round and cross a wall from outside);
+  // 0 (A/B): the proof gives up there.  Read by occ_exit alone, where the proof would give up
+  uint32_t shadow_reentry;
+  uint32_t reentry_pad;
 #if RRT_PROFILE
   // diagnostic build: per-wave progress records in host-coherent memory (RRT_WATCHDOG_MS), read by
   // the host while the kernels run: [wave][4] = {iteration, state, pixel, marker}; batch waves

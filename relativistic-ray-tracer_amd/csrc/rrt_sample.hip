@@ -122,11 +122,13 @@ __device__ __forceinline__ spec direct_hemisphere_lds(const KParams& kp, Rng& g,
 
 #if RRT_PROFILE
 // [0..7] per-phase wave cycles (busiest lane per wave, summed): total, camera queries, micro
-// steps, camera walks, miss proofs, shadow queries, shadow walks, -; [8] min start, [9] max end,
+// steps, camera walks, miss proofs, shadow queries (the occlusion proof included), shadow walks, the
+// shadow rays' occlusion proof alone; [8] min start, [9] max end,
 // [10] waves, [11] first exhaustion (wall clock); [16..19] batch-kernel phases: claims, chain
-// walks, shading, fold; then per-wave end / start / work records
-#define RRT_PROF_HDR 24
+// walks, shading, fold; [12..15], [20..24] lane sums; then per-wave end / start / work records
+#define RRT_PROF_HDR 32
 __device__ unsigned long long rrt_prof[RRT_PROF_HDR];
+extern "C" int rrt_prof_hdr(void) { return RRT_PROF_HDR; }  // rrt_prof_read's header words
 __device__ unsigned long long rrt_prof_ends[16384], rrt_prof_starts[16384], rrt_prof_work[16384];
 // slowest pixels: bucket (pixel slot % 64) keeps max(elapsed wall ticks << 24 | slot)
 __device__ unsigned long long rrt_prof_slow[64];
@@ -329,7 +331,7 @@ __global__ __launch_bounds__(256, WAVES) void rrt_sample_kernel(const KParams* _
   }
 #if RRT_PROFILE
   const uint64_t t_end = clock64(), w_end = wall_clock64();
-  uint64_t v[8] = {t_end - t_start, cn.t_query, cn.t_micro, cn.t_trav, cn.t_proof, cn.t_squery, cn.t_strav, 0};
+  uint64_t v[8] = {t_end - t_start, cn.t_query, cn.t_micro, cn.t_trav, cn.t_proof, cn.t_squery, cn.t_strav, cn.t_sproof};
   uint32_t ns = prof_samples;
   for (int off = 32; off > 0; off >>= 1) ns += __shfl_xor(ns, off);
   prof_wave_record(v, lane, w_start, w_end, ((unsigned long long)prof_blocks << 32) | ns);
@@ -1079,12 +1081,12 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
 #endif
 #if RRT_PROFILE
   const uint64_t t_end = clock64(), w_end = wall_clock64();
-  uint64_t v[12] = {t_end - t_start, cn.t_query, cn.t_micro, cn.t_trav, cn.t_proof, cn.t_squery, cn.t_strav, 0,
+  uint64_t v[12] = {t_end - t_start, cn.t_query, cn.t_micro, cn.t_trav, cn.t_proof, cn.t_squery, cn.t_strav, cn.t_sproof,
                     cn.t_claim, cn.t_chain, cn.t_shade, cn.t_fold};
   {  // lane sums of the phases (slot 12 + i): a phase's lane use = lane sum / (64 x busiest lane)
-    const int ks[8] = {0, 1, 2, 3, 4, 5, 6, 10};
-    const int slot[8] = {15, 12, 23, 21, 14, 13, 22, 20};
-    for (int i = 0; i < 8; ++i) {
+    const int ks[9] = {0, 1, 2, 3, 4, 5, 6, 10, 7};
+    const int slot[9] = {15, 12, 23, 21, 14, 13, 22, 20, 24};
+    for (int i = 0; i < 9; ++i) {
       uint64_t sm = v[ks[i]];
       for (int off2 = 32; off2 > 0; off2 >>= 1) sm += __shfl_xor(sm, off2);
       if (lane == 0) atomicAdd(&rrt_prof[slot[i]], (unsigned long long)sm);

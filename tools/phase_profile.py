@@ -66,7 +66,7 @@ def main():
     n = len(tiles) * 1024
     prgb = torch.zeros(n * 3, dtype=torch.float32, device="cuda")
     pcnt = torch.zeros(n, dtype=torch.int32, device="cuda")
-    HDR = 24
+    HDR = L.rrt_prof_hdr() if hasattr(L, "rrt_prof_hdr") else 24  # a build from before the shadow_proof counter
     buf = np.zeros(HDR + 3 * 16384, np.uint64)
     out = {}
     for fl in a.flags:
@@ -81,7 +81,7 @@ def main():
             r.render_tiles_device(p, tiles, 32, prgb.data_ptr(), pcnt.data_ptr())
         ms = r.stats().last_kernel_ms
         L.rrt_prof_read(buf.ctypes.data)
-        tot, tq, tm, tt, tp, tsq, tst = (float(v) for v in buf[:7])
+        tot, tq, tm, tt, tp, tsq, tst, tsp = (float(v) for v in buf[:8])
         t0, t1, nw, tex = int(buf[8]), int(buf[9]), int(buf[10]), int(buf[11])
         span = t1 - t0
         m = min(nw, 16384)
@@ -124,6 +124,8 @@ def main():
                    "exhausted_at": (tex - t0) / span, "wave_cycles": tot,
                    "camera_query": tq / tot, "micro_all": tm / tot, "camera_walk": tt / tot,
                    "miss_proof": tp / tot, "shadow_query": tsq / tot, "shadow_walk": tst / tot,
+                   # the occlusion proof's part of shadow_query; the rest is the exact marches
+                   "shadow_proof": tsp / tot, "shadow_exact": (tsq - tsp) / tot,
                    "outside_queries_and_proof": 1 - (tq + tp + tsq) / tot,
                    "claim": float(buf[16]) / tot, "chain": float(buf[17]) / tot, "shade_incl_shadow": float(buf[18]) / tot,
                    "fold": float(buf[19]) / tot,
@@ -131,6 +133,7 @@ def main():
                    "lane_use": {k: float(buf[i]) / (64.0 * float(buf[j])) if buf[j] else None for k, i, j in
                                 (("total", 15, 0), ("camera_query", 12, 1), ("micro", 23, 2), ("camera_walk", 21, 3),
                                  ("miss_proof", 14, 4), ("shadow_query", 13, 5), ("shadow_walk", 22, 6),
+                                 *((("shadow_proof", 24, 7),) if HDR > 24 else ()),
                                  ("shade", 20, 18))},
                    "slowest_pixels": slow_px,
                    "busy_frac_working_waves": float(((ends - starts)[res]).sum() / max(res.sum(), 1)),

@@ -5,7 +5,14 @@ envelope the library enables the proofs in (include/rrt.h RRT_PROOF_*: delta_the
 [0.04, 0.6], r_s <= 0.5 x the room's largest extent) and beyond it (delta_theta in [0.005, 1.2],
 r_s up to 1.5 x the room's extent), reporting per proof the share proven, the smallest headroom
 (margin / deviation of the recurrence from the reference's march) and violations (a proven ray or
-pixel the reference's march contradicts).  TEST INFRASTRUCTURE (CPU, oracle restatement)."""
+pixel the reference's march contradicts).  TEST INFRASTRUCTURE (CPU, oracle restatement).
+
+--shadow-mirror reentry: the shadow check alone, with the re-entry rule's mirror
+(tests/shadow_reentry_sim.py) beside the old one, on the configurations recorded in --configs-from
+(their scenes, holes and root boxes; default profiles/r03_proof_sweep.json, both sweeps) ->
+profiles/shadow_reentry_sweep.json: rays, proven before and after, proven after leaving the root
+box, the worst deviation over the margin, violations, and rays the old rule proved that the new one
+does not prove at the same row and triangle."""
 import argparse
 import json
 import os
@@ -31,12 +38,49 @@ def summary(res):
     return out
 
 
+def reentry_summary(rows):
+    out = {"configs": len(rows)}
+    for k in ("rays", "proven_before", "proven_after", "proven_after_leaving", "violations", "lost"):
+        out[k] = sum(r[k] for r in rows)
+    out["worst_dev_over_margin"] = max((r["worst_dev_over_margin"] for r in rows), default=0.0)
+    return out
+
+
+def reentry_sweep(a):
+    import numpy as np
+    import shadow_reentry_sim as R
+    with open(a.configs_from) as f:
+        rec = json.load(f)
+    t0 = time.time()
+    out = {"envelope": rec["envelope"], "configs_from": os.path.relpath(a.configs_from, ROOT)}
+    for part, seed, n in (("inside", 2024, 600), ("beyond", 4048, 400)):
+        g = np.random.default_rng(seed)
+        rows = []
+        for i, c in enumerate(rec["configs_" + part]):
+            sf, lo, hi = P._scene(c["scene"])
+            r = R.check_config({"sf": sf, "lo": lo, "hi": hi, "bh": np.array(c["bh"], np.float64)}, n, g)
+            rows.append(dict(scene=c["scene"], bh=c["bh"], **r))
+            print(part, i, c["scene"], [round(v, 3) for v in c["bh"]], r, flush=True)
+        out[part] = reentry_summary(rows)
+        out["configs_" + part] = rows
+    out["seconds"] = time.time() - t0
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps({k: out[k] for k in ("envelope", "inside", "beyond", "seconds")}, indent=1))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", type=int, default=240)
     ap.add_argument("--beyond", type=int, default=120)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r03_proof_sweep.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--shadow-mirror", choices=["plain", "reentry"], default="plain")
+    ap.add_argument("--configs-from", default=os.path.join(ROOT, "profiles", "r03_proof_sweep.json"))
     a = ap.parse_args()
+    if a.shadow_mirror == "reentry":
+        a.out = a.out or os.path.join(ROOT, "profiles", "shadow_reentry_sweep.json")
+        return reentry_sweep(a)
+    a.out = a.out or os.path.join(ROOT, "profiles", "r03_proof_sweep.json")
     t0 = time.time()
 
     def log(i, r):
