@@ -60,7 +60,7 @@ constexpr size_t kCounterBytes = sizeof(uint32_t) * RRT_QUEUE_STRIDE * (RRT_MAX_
 // Heavy pixels (rrt_sample.hip heavy_pixel_block): rays passing within RRT_HEAVY_NEAR r_s of the hole (or straddling
 // its capture boundary) make a pixel heavy (profiles/r03_heavy_ab.md)
 #define RRT_HEAVY_NEAR 1.2
-// Kerr occlusion proof (rrt_device.h kerr_occluded_proof): coarse steps RRT_KPROOF_STRETCH times the
+// Kerr occlusion proof (rrt_proof.h kerr_occluded_proof): coarse steps RRT_KPROOF_STRETCH times the
 // march's, no proof within RRT_KPROOF_NEAR_M M of the hole, crossing margin RRT_KPROOF_DELTA_M M;
 // on for holes with delta_theta in [DT_MIN, DT_MAX], a/M <= SPIN_MAX and every root-box corner
 // within REACH_M M -- the envelope tools/kerr_proof_sweep.py swept (tests/test_kerr_proof.py)
@@ -475,7 +475,7 @@ static bool grid_mark_leaf(const rrt_ctx* c, const double g0[3], double h, const
   return true;
 }
 
-// Shadow-ray occlusion proof (rrt_device.h shadow_occluded_proof): the large triangles within 1%
+// Shadow-ray occlusion proof (rrt_proof.h shadow_occluded_proof): the large triangles within 1%
 // of the scene's extent of a root-box face and facing along its axis (walls; CBempty's back wall
 // sits 0.2% inside the box), taken as the reference intersects them (p0, p0 + e1, p0 + e2),
 // largest first, RRT_OCC_PER_FACE per face, none under 5% of the face's largest: plane (normal
@@ -1631,7 +1631,7 @@ static void fill_scene_params(const rrt_ctx* c, uint32_t flags, KParams& kp) {
 // shadow proof's re-entry rule, from the launch's A/B knobs (plan_shadow_reentry).
 static bool fill_proof_params(const rrt_ctx* c, uint32_t flags, uint32_t shadow_reentry, KParams& kp) {
   bool proofs_valid = false;
-  {  // camera-ray miss proof constants (rrt_device.h camera_miss_proof)
+  {  // camera-ray miss proof constants (rrt_proof.h camera_miss_proof)
     const DHole& h = kp.hole;
     DMissProof& mp = kp.miss;
     const Box& rb = c->nodes[0].bb;
@@ -1678,9 +1678,9 @@ static bool fill_proof_params(const rrt_ctx* c, uint32_t flags, uint32_t shadow_
     // the point-light scenes' builds carry no proof (rrt_sample.hip RRT_OCC_TAG); off for them in
     // every kernel, so the counting passes count what their batch kernel executes
     kp.occ.on = (proofs_valid && any && fin && c->lean != 2 && !(flags & RRT_RENDER_NO_SHADOW_PROOF)) ? 1u : 0u;
-    // a ray that has left the root box goes on with the proof (rrt_device.h occ_exit); 0 (A/B): it gives up
+    // a ray that has left the root box goes on with the proof (rrt_proof.h occ_exit); 0 (A/B): it gives up
     kp.shadow_reentry = shadow_reentry;
-    // Kerr shadow rays (rrt_device.h kerr_occluded_proof): the same face triangles
+    // Kerr shadow rays (rrt_proof.h kerr_occluded_proof): the same face triangles
     // against a coarse march, inside the envelope its margin was swept over
     // (tools/kerr_proof_sweep.py -> profiles/r04_kerr_proof_sweep.json)
     DKerrProof& kq = kp.kproof;
@@ -1916,7 +1916,7 @@ static void plan_batch(const rrt_ctx* c, const rrt_render_params* p, const AbKno
     return;
   pl.list_n = pl.n_pixels;
   kp.claim_back = ab.claim_fwd ? 0u : 1u;  // hit-first claim order (rrt_pixel_proof_kernel)
-  // Heavy pixels (rrt_device.h pixel_heavy): the pass lists them apart and rrt_heavy_kernel
+  // Heavy pixels (rrt_proof.h pixel_heavy): the pass lists them apart and rrt_heavy_kernel
   // renders them slot-parallel, a block of waves per pixel (rrt_sample.hip
   // heavy_pixel_block); needs a hit to take a whole number of slots (Dh = k Dm)
   // Where the heavy pixels' latency bounds the launch: launches covering at most 60% of the

@@ -191,7 +191,7 @@ struct DGrid {
   int32_t pad;
 };
 
-// Camera-ray miss proof (rrt_device.h camera_miss_proof): the constants of the
+// Camera-ray miss proof (rrt_proof.h camera_miss_proof): the constants of the
 // planar recurrence that the reference's Schwarzschild march follows, and the margins.
 struct DMissProof {
   double co1, si1;        // cos_dt / rho, sin_dt / rho  (rho = |(cos_dt, sin_dt)|)
@@ -206,7 +206,7 @@ struct DMissProof {
   uint32_t on, pad;
 };
 
-// Shadow-ray occlusion proof (rrt_device.h shadow_occluded_proof): triangles that
+// Shadow-ray occlusion proof (rrt_proof.h shadow_occluded_proof): triangles that
 // lie along the root box's faces (a Cornell box's walls), as the reference intersects them
 // (p0, p0 + e1, p0 + e2).  Face f: axis f % 3, the box's low face for f < 3, else its high face.
 // n . x - d: signed distance from the triangle's plane, positive on the box's inner side;
@@ -223,7 +223,7 @@ struct DShadowProof {
   uint32_t on, pad;
 };
 
-// Kerr shadow-ray occlusion proof (rrt_device.h kerr_occluded_proof): a coarse march
+// Kerr shadow-ray occlusion proof (rrt_proof.h kerr_occluded_proof): a coarse march
 // (steps stretch x delta_theta x r) whose chords the exact march's stay within delta of
 // A wall piece of the Kerr proof: an occluder triangle, or two coplanar ones of the same face that
 // share an edge and form a convex quad (a Cornell-box wall), as one convex polygon: plane (normal
@@ -419,7 +419,7 @@ struct KParams {
   // [2 k + 1] violations per proof k (RRT_AUDIT_*); null: no audit
   RRT_GLOBAL_AS unsigned long long* audit;  // 64-bit: a 1080p frame audited at every_log2 = 0 exceeds 2^32 checks
   uint32_t audit_shift;
-  // pixel pass (rrt_device.h rect_miss_proof): 1: a row near the root box tries the
+  // pixel pass (rrt_proof.h rect_miss_proof): 1: a row near the root box tries the
   // separating half-space rule before the widened slab test; 0 (A/B): the slab test alone
   uint32_t halfspace;
   // continuations: a batch-kernel group whose pixel still has >= cont_min_left
@@ -436,7 +436,7 @@ struct KParams {
                           // leave once the heavy list is done (their slots go back to the batch kernel)
   DDisk disk;             // the accretion disk (every earlier field keeps its offset)
   DObs obs;               // the moving observer (behind the disk: every earlier field keeps its offset)
-  // shadow-ray occlusion proof (rrt_device.h occ_exit): 1: a ray whose segment end has left
+  // shadow-ray occlusion proof (rrt_proof.h occ_exit): 1: a ray whose segment end has left
   // the root box without a certain crossing goes on (it may turn round and cross a wall from outside);
   // 0 (A/B): the proof gives up there.  Read by occ_exit alone, where the proof would give up
   uint32_t shadow_reentry;

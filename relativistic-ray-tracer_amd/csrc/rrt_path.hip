@@ -73,7 +73,7 @@ struct OwnLds {
 
 }  // namespace rrt
 
-// The shadow-ray occlusion proof's build tag for this kernel (rrt_device.h query_nx / occ_exit_call)
+// The shadow-ray occlusion proof's build tag for this kernel (rrt_proof.h query_nx / occ_exit_call)
 #define RRT_OCC_TAG_PATH(WAVES) (512 + (WAVES))
 
 namespace rrt {

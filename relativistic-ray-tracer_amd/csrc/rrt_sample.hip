@@ -46,7 +46,7 @@ __device__ __forceinline__ void park_hit(RRT_LDS SL& cl, uint32_t t, const Isect
 
 // estimate_direct_lighting_importance (part1_code.cpp:33-57) for the hit parked in LDS
 // (park_hit), re-read per light sample so no hit state stays live across the shadow queries.
-// W: the calling kernel build's tag for the out-of-line occlusion proof (rrt_device.h query_nx)
+// W: the calling kernel build's tag for the out-of-line occlusion proof (rrt_proof.h query_nx)
 // SCOPED: the LEAN batch / heavy builds' shadow queries (rrt_device.h kp_stage)
 template <bool COUNT, int LEAN, int W = 0, class SL = ShadeLds, bool SCOPED = false>
 __device__ __forceinline__ spec direct_importance_parked(const KParams& kp, Rng& g, RRT_LDS SL& cl, uint32_t t, Counters& cn) {
@@ -111,7 +111,7 @@ __device__ __forceinline__ spec direct_hemisphere_lds(const KParams& kp, Rng& g,
 
 }  // namespace rrt
 
-// The shadow-ray occlusion proof's build tag (rrt_device.h query_nx): the area-light and the
+// The shadow-ray occlusion proof's build tag (rrt_proof.h query_nx): the area-light and the
 // general builds (cfg1-3; scenes with environment maps or BSDF sampling); not the point-light
 // build (cfg4: its frame is the camera rays' -- 98% proven misses -- and carrying the proof's code
 // cost it 10%, more than the proof saved) nor the Kerr builds (no planar recurrence).  One tag per
@@ -377,7 +377,7 @@ struct GroupLds {  // group size >= 8: at most 32 groups per 256-thread block
   uint8_t sst[32][NSLOTS], sown[32][NSLOTS];
 };
 
-// Heavy pixel hx of the pixel proof pass's heavy list (rrt_device.h pixel_heavy),
+// Heavy pixel hx of the pixel proof pass's heavy list (rrt_proof.h pixel_heavy),
 // rendered by one block of NW waves: its 64 NW consecutive draw-offset slots per round, in
 // parallel.  Sample k of a pixel starts at draw offset Dm * m_k with m_0 = 0 and m_{k+1} = m_k +
 // (hit_k ? Dh / Dm : 1) (the slots below, counted from the pixel's first draw), so slot m's
@@ -474,7 +474,7 @@ template <int LEAN, int W, int NW>
 __device__ __noinline__ void heavy_pixel_block(const RRT_CONST_AS KParams* kpq, rrt::ShadeLdsN<64 * NW>& sh_gen,
                                                HeavyState<NW>& hs_gen, uint32_t t, rrt::Counters& cn) {
   using namespace rrt;
-  // the launch block, by its address space and in SGPRs (rrt_device.h occ_exit_call)
+  // the launch block, by its address space and in SGPRs (rrt_proof.h occ_exit_call)
   const KParams& kp = *(const KParams*)uniform_ptr(kpq);
   // the callers' __shared__ HeavyLds members (rrt_heavy_kernel's `hl`), handed over as generic
   // references: an out-of-line callee takes no LDS-qualified pointer
@@ -1098,7 +1098,7 @@ __global__ __launch_bounds__(256, WAVES) void rrt_batch_kernel(const KParams* __
 #endif
 }
 
-// Pixel miss proof pass (rrt_device.h pixel_miss_proof), one lane per claim index
+// Pixel miss proof pass (rrt_proof.h pixel_miss_proof), one lane per claim index
 // in the batch kernel's order: a pixel whose every camera ray is a proven miss renders to black
 // (no environment map in these builds): its samples are all zero, so it stops at the first
 // adaptive check (raytrace_pixel, part1_code.cpp:147-158) with count = min(ns_aa,

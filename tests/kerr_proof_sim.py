@@ -1,4 +1,4 @@
-"""Mirror of the Kerr shadow-ray occlusion proof (relativistic-ray-tracer_amd/csrc/rrt_device.h
+"""Mirror of the Kerr shadow-ray occlusion proof (relativistic-ray-tracer_amd/csrc/rrt_proof.h
 kerr_occluded_proof, constants from rrt_host.cpp RRT_KPROOF_*), one ray at a time, on the CPU
 restatement's coarse march (oracle/restate ro_kerr_chain_st: the same Hamiltonian, RK4 and step
 rule as the device's, steps `stretch` times longer).

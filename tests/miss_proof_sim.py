@@ -1,4 +1,4 @@
-"""numpy mirror of the camera-ray miss proof (relativistic-ray-tracer_amd/csrc/rrt_device.h
+"""numpy mirror of the camera-ray miss proof (relativistic-ray-tracer_amd/csrc/rrt_proof.h
 camera_miss_proof), vectorised over rays, with the per-point trace the deviation checks need.
 
 TEST INFRASTRUCTURE ONLY (tests/test_miss_proof.py): the product runs the HIP version.
@@ -71,6 +71,55 @@ def seg_clear(a, b, lo, hi, m):
     return out | (tmin > tmax + 1e-9)
 
 
+# The planar recurrence and its geometry, stated once for the five mirrors (this module's run,
+# shadow_proof_sim.run, shadow_reentry_sim.run, pixel_proof_sim.prove, rect_proof_sim.prove).  Each
+# takes arrays (one entry per ray, or per recurrence of a pixel) or scalars.
+
+def rec_row(K, vprev, s):
+    """One row from the last v and the s of the step that made it: (u', s, v) of the next step
+    (blackhole.cpp:23-32 on (s, u'))."""
+    def f(u):
+        return -u + K["k15"] * u * u
+
+    up = (vprev * K["co1"] - K["rho"] * s) / K["si"]
+    s = np.abs(vprev) / K["rho"]
+    f1 = f(s)
+    u2 = s + up * (K["dt"] * 0.5)
+    u3 = u2 + f1 * (K["dt"] * K["dt"] / 4.0)
+    return up, s, s + up * K["dt"] + (f1 + f(u2) + f(u3)) * (K["dt"] * K["dt"] / 6.0)
+
+
+def rec_cancels(K, s, up, v):
+    """A cancelling step (or NaN): the recurrence is not certain to follow the reference there."""
+    return ~(np.abs(v) >= KAPPA * (s + np.abs(up) * K["dt"]))
+
+
+def rec_turn(K, sg, sig, ea, eb):
+    """The frame turn: (na, nb, the next sig) from the step's sense sg = sign(vprev)."""
+    a = sg * K["co1"]
+    b = sig * K["si1"]
+    return a * ea - b * eb, a * eb + b * ea, sig * sg
+
+
+def rec_line_den(K, vprev, v):
+    """D: the line through a segment's ends lies at distance^2 sin^2 dt / D from the hole."""
+    return v * v + vprev * vprev - 2.0 * K["co1"] * np.abs(vprev) * v
+
+
+def rec_hole_farther(K, vprev, v, d2):
+    """The segment's distance^2 from the hole exceeds d2: the line's where the foot of the
+    perpendicular falls inside the segment, else the nearer end's."""
+    avp = np.abs(vprev)
+    D = rec_line_den(K, vprev, v)
+    inside = (v * (K["co1"] * avp - v) < 0.0) & (avp * (avp - K["co1"] * v) > 0.0)
+    return np.where(inside, K["si"] * K["si"] > d2 * D, K["rho"] ** 2 > d2 * np.maximum(v * v, vprev * vprev))
+
+
+def rec_point(K, X, Y, ea, eb, v):
+    """c + (rho / v) (ea X + eb Y)."""
+    return K["c"] + np.asarray(ea * K["rho"] / v)[..., None] * X + np.asarray(eb * K["rho"] / v)[..., None] * Y
+
+
 def run(K, o, d, step0_clear):
     """The proof for rays (o, d).  step0_clear[i]: the reference's root test fails on segment 0.
     Returns (proven [n], points [steps+1, n, 3] of the recurrence (NaN once a ray bails),
@@ -86,34 +135,19 @@ def run(K, o, d, step0_clear):
     eb = np.full(n, K["si1"])
     sig = np.ones(n)
     rp = K["rho"] / np.abs(vprev)
-    si2 = K["si"] * K["si"]
     far_steps = 0
     with np.errstate(all="ignore"):
         for j in range(1, steps):
             sg = np.where(vprev < 0.0, -1.0, 1.0)
-            up = (vprev * K["co1"] - K["rho"] * s) / K["si"]
-            s = np.abs(vprev) / K["rho"]
-            f1 = -s + K["k15"] * s * s
-            u2 = s + up * (K["dt"] * 0.5)
-            f2 = -u2 + K["k15"] * u2 * u2
-            u3 = u2 + f1 * (K["dt"] * K["dt"] / 4.0)
-            f3 = -u3 + K["k15"] * u3 * u3
-            v = s + up * K["dt"] + (f1 + f2 + f3) * (K["dt"] * K["dt"] / 6.0)
-            alive &= np.abs(v) >= KAPPA * (s + np.abs(up) * K["dt"])
-            a = sg * K["co1"]
-            b = sig * K["si1"]
-            na = a * ea - b * eb
-            nb = a * eb + b * ea
-            sig = sig * sg
-            av, avp = np.abs(v), np.abs(vprev)
-            r = K["rho"] / av * (1.0 + 1e-6)
+            up, s, v = rec_row(K, vprev, s)
+            alive &= ~rec_cancels(K, s, up, v)
+            na, nb, sig = rec_turn(K, sg, sig, ea, eb)
+            r = K["rho"] / np.abs(v) * (1.0 + 1e-6)
             m = ETA * (np.maximum(rp, r) + K["scale"])
             rb = K["r_ball"] + m
-            D = v * v + vprev * vprev - 2.0 * K["co1"] * avp * v
-            inside = (v * (K["co1"] * avp - v) < 0.0) & (avp * (avp - K["co1"] * v) > 0.0)
-            far = np.where(inside, si2 > rb * rb * D, K["rho"] ** 2 > rb * rb * np.maximum(v * v, vprev * vprev))
-            pa = K["c"] + (ea * K["rho"] / vprev)[:, None] * X + (eb * K["rho"] / vprev)[:, None] * Y
-            p = K["c"] + (na * K["rho"] / v)[:, None] * X + (nb * K["rho"] / v)[:, None] * Y
+            far = rec_hole_farther(K, vprev, v, rb * rb)
+            pa = rec_point(K, X, Y, ea, eb, vprev)
+            p = rec_point(K, X, Y, na, nb, v)
             alive &= far | seg_clear(pa, p, K["lo"], K["hi"], m)
             far_steps += int((far & alive).sum())
             pts[j + 1] = np.where(alive[:, None], p, np.nan)

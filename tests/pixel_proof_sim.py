@@ -1,4 +1,4 @@
-"""numpy mirror of the pixel miss proof (relativistic-ray-tracer_amd/csrc/rrt_device.h
+"""numpy mirror of the pixel miss proof (relativistic-ray-tracer_amd/csrc/rrt_proof.h
 pixel_miss_proof), one pixel at a time, given the pixel's centre and corner ray directions.
 
 TEST INFRASTRUCTURE ONLY (tests/test_pixel_proof.py): the product runs the HIP version.
@@ -11,7 +11,7 @@ clear the root box by the camera proof's margin plus that bound.
 """
 import numpy as np
 
-from miss_proof_sim import ETA, KAPPA, seg_clear
+from miss_proof_sim import ETA, rec_cancels, rec_line_den, rec_point, rec_row, rec_turn, seg_clear
 
 
 def prove(K, O, dc, corners):
@@ -58,23 +58,14 @@ def prove(K, O, dc, corners):
     si2 = K["si"] * K["si"]
     rho = K["rho"]
     for j in range(K["steps"]):
-        up = (vp * K["co1"] - rho * s) / K["si"]
-        s = np.abs(vp) / rho
-        f1 = -s + K["k15"] * s * s
-        u2 = s + up * (K["dt"] * 0.5)
-        f2 = -u2 + K["k15"] * u2 * u2
-        u3 = u2 + f1 * (K["dt"] * K["dt"] / 4.0)
-        f3 = -u3 + K["k15"] * u3 * u3
-        v = s + up * K["dt"] + (f1 + f2 + f3) * (K["dt"] * K["dt"] / 6.0)
-        ok = bool(np.all(np.abs(v) >= KAPPA * (s + np.abs(up) * K["dt"])))
+        up, s, v = rec_row(K, vp, s)
+        ok = not np.any(rec_cancels(K, s, up, v))
         dv = 1.5 * max(abs(v[0] - v[1]), abs(v[2] - v[1]))
         av = abs(v[1])
         if not (ok and (v[0] < 0) == (v[1] < 0) and (v[2] < 0) == (v[1] < 0) and av > 2.0 * dv):
             return False
         sg = -1.0 if vp[1] < 0.0 else 1.0
-        a, b = sg * K["co1"], sig * K["si1"]
-        na, nb = a * ea - b * eb, a * eb + b * ea
-        sig *= sg
+        na, nb, sig = rec_turn(K, sg, sig, ea, eb)
         r = rho / (av - dv) * (1.0 + 1e-6)
         dpb = rho * dv / (av * (av - dv)) * (1.0 + 1e-6) + r * abs(nb) * dY
         m0 = ETA * (max(rp, r) + K["scale"])
@@ -84,11 +75,10 @@ def prove(K, O, dc, corners):
         for k in range(4):
             w = v[1] + (dv if k & 1 else -dv)
             wp = vp[1] + (dvp if k & 2 else -dvp)
-            D = w * w + wp * wp - 2.0 * K["co1"] * abs(wp) * w
-            far = far and si2 > rb * rb * D  # the line distance, a lower bound on the segment's
+            far = far and si2 > rb * rb * rec_line_den(K, wp, w)  # the line distance, a lower bound on the segment's
         if not far:
-            pa = O if j == 0 else c + (ea * rho / vp[1]) * X + (eb * rho / vp[1]) * Yc
-            pb = c + (na * rho / v[1]) * X + (nb * rho / v[1]) * Yc
+            pa = O if j == 0 else rec_point(K, X, Yc, ea, eb, vp[1])
+            pb = rec_point(K, X, Yc, na, nb, v[1])
             if not seg_clear(pa[None], pb[None], K["lo"], K["hi"], np.array([m]))[0]:
                 return False
         vp = v

@@ -1,4 +1,4 @@
-"""Soundness sweep of the three result-identical proofs (rrt_device.h camera_miss_proof,
+"""Soundness sweep of the three result-identical proofs (rrt_proof.h camera_miss_proof,
 pixel_miss_proof, shadow_occluded_proof) beyond the BASELINE framings.
 
 TEST INFRASTRUCTURE ONLY (tools/proof_sweep.py writes profiles/r03_proof_sweep.json;

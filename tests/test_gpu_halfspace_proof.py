@@ -1,4 +1,4 @@
-"""GPU: the pixel pass's separating half-space rule (rrt_device.h rect_miss_proof, DESIGN.md §5;
+"""GPU: the pixel pass's separating half-space rule (rrt_proof.h rect_miss_proof, DESIGN.md §5;
 launch constant KParams::halfspace, A/B knob RRT_AB_NO_HALFSPACE read at every launch).
 
 Two 64 x 64 regions of the cfg3 frame at its full 1920 x 1080 framing and 64 spp -- tiles of 32 at

@@ -1,4 +1,4 @@
-"""GPU: the shadow-ray occlusion proof's re-entry rule (rrt_device.h occ_exit; launch
+"""GPU: the shadow-ray occlusion proof's re-entry rule (rrt_proof.h occ_exit; launch
 constant KParams::shadow_reentry, A/B knob RRT_AB_NO_SHADOW_REENTRY read at every launch).
 
 The two smallest framings that hold shadow rays which leave the room past the hole and come back

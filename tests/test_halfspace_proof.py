@@ -1,4 +1,4 @@
-"""The pixel pass's separating half-space rule (rrt_device.h rect_miss_proof; numpy
+"""The pixel pass's separating half-space rule (rrt_proof.h rect_miss_proof; numpy
 mirror tests/rect_proof_sim.py) against the CPU restatement of the reference's march (oracle
 ro_camera_ray / ro_micro_chain), on random pixels and 8 x 8 strips of the BASELINE framings:
 

@@ -1,4 +1,4 @@
-"""The Kerr shadow-ray occlusion proof (rrt_device.h kerr_occluded_proof) on the CPU
+"""The Kerr shadow-ray occlusion proof (rrt_proof.h kerr_occluded_proof) on the CPU
 restatement's marches (tests/kerr_proof_sim.py mirrors the device proof on ro_kerr_chain_st):
 
 * the host's Kerr envelope constants are the mirror's;

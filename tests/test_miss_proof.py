@@ -1,4 +1,4 @@
-"""The camera-ray miss proof (rrt_device.h camera_miss_proof) against the CPU
+"""The camera-ray miss proof (rrt_proof.h camera_miss_proof) against the CPU
 restatement of the reference's march (oracle ro_micro_chain, bit-exact with blackhole.cpp /
 bvh.cpp): on random jittered camera rays of every BASELINE framing,
 

@@ -1,4 +1,4 @@
-"""The pixel miss proof (rrt_device.h pixel_miss_proof) against the CPU restatement
+"""The pixel miss proof (rrt_proof.h pixel_miss_proof) against the CPU restatement
 of the reference's march (oracle ro_camera_ray / ro_micro_chain, bit-exact with
 part1_code.cpp:182-187 and blackhole.cpp / bvh.cpp): on random pixels of the BASELINE framings,
 

@@ -1,4 +1,4 @@
-"""The shadow-ray occlusion proof (rrt_device.h shadow_occluded_proof) against the
+"""The shadow-ray occlusion proof (rrt_proof.h shadow_occluded_proof) against the
 CPU restatement of the reference's march (oracle ro_micro_chain / ro_tri_intersect, bit-exact with
 blackhole.cpp / bvh.cpp / triangle.cpp), on shadow rays from random surface points of the BASELINE
 Cornell-box scenes towards random points of their area lights:

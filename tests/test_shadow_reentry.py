@@ -1,4 +1,4 @@
-"""The shadow-ray occlusion proof's re-entry rule (rrt_device.h occ_exit, KParams::shadow_reentry;
+"""The shadow-ray occlusion proof's re-entry rule (rrt_proof.h occ_exit, KParams::shadow_reentry;
 DESIGN.md §5; numpy mirror tests/shadow_reentry_sim.py) against the CPU restatement of the
 reference's march (oracle ro_micro_chain / ro_tri_intersect / ro_shadow_query).
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Sweep of the Kerr shadow-ray occlusion proof's margin (rrt_device.h kerr_occluded_proof,
+"""Sweep of the Kerr shadow-ray occlusion proof's margin (rrt_proof.h kerr_occluded_proof,
 rrt_host.cpp RRT_KPROOF_*) over its envelope, on the CPU restatement (tests/kerr_proof_sim.py):
 random holes (r_s, delta_theta, spin a/M, spin axis, position) in the Cornell-box scenes, random
 shadow rays from surface points.  For every ray the proof calls occluded, the restatement's exact

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Sweep of the pixel pass's strip level (rrt_device.h rect_miss_proof on 8x8 strips, the numpy
+"""Sweep of the pixel pass's strip level (rrt_proof.h rect_miss_proof on 8x8 strips, the numpy
 mirror tests/pixel_proof_sim.py): random 8x8-aligned strips of a BASELINE framing; every pixel of
 every proven strip -- its four corners and two random jitters -- is marched by the oracle
 (ro_micro_chain, bit-exact with the reference), and no segment of it may come near the root box
